@@ -2,6 +2,8 @@
 """bench.py - MiCo omni-modal alignment step (ViT-g/14 fwd+bwd) on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full                  (also every figure beyond the headline, see below)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR      (also the last timed step's outputs as DIR/*.npy)
     python bench.py --gpus 8 --steps 20 --warmup 3          (launches its own 8 ranks, one per GPU, when not already under torchrun)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -14,20 +16,24 @@ for both sub-tasks + causal masked-caption LM; step-B of SURVEY.md section 8d). 
 N = 8 line (weak scaling: every rank runs this on its own shard, the contrastive features are exchanged with one packed RCCL
 all-gather, hard-negative condition rows with an index-then-fetch all-to-all, gradients averaged with bucketed all-reduces overlapped
 with the backward).  `secondary.configs2_img_aud_txt` is BASELINE configs[2] (image + audio + text, b = 64: rounds 1-3's headline)
-timed in the same run; `--workload img_aud_txt` makes it the headline again.
+timed in the same run with --full; `--workload img_aud_txt` makes it the headline again.
 
 Precision of the timed run (--dtype): fp16 MFMA operands, fp32 accumulation / residual stream / statistics - the 16-bit type the
-reference's own trainer runs in (fp16 autocast, data/utils/pipeline.py:43) at the bf16 MFMA rate.  `parity` in the JSON line holds
+reference's own trainer runs in (fp16 autocast, data/utils/pipeline.py:43) at the bf16 MFMA rate.  `parity` in the --full line holds
 max|out - ref| / max|ref| of exactly this configuration against the reference-generated goldens (tests/golden/vit_g14_*.pt), measured
 in the same process after the timed region - ViT tokens / feat_v, BERT sequence outputs and loss, feat_t / sim logits / ITM scores of the
 facade and the three alignment losses; `parity_config` is the same step timed in the configuration with margin under the 1e-3 gate (fp16
 with hi/lo-split weights: 2 k-segments per forward GEMM) next to it.
 
-One JSON line on rank 0 (see the repo prompt for the field contract) with extra objects:
-  roofline     - the dominant kernel (MFMA GEMM) timed per launch with HIP events inside the timed region;
+One JSON line on rank 0: the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step,
+steps, warmup, ...) and
+  roofline     - the dominant kernel (MFMA GEMM) timed per launch with HIP events inside the timed region, and the step's MFMA fraction.
+A plain run does nothing else: set-up, --warmup untimed steps, exactly --steps timed ones, the line.  --full adds, after the timed steps:
   cpu_baseline - the CPU oracle (oracle/mico_oracle.py, a restatement of the reference parity-locked to it) timed on the
                  host cores on a bounded sample of the same workload plus the BASELINE.md section 4 anchors (rank 0, N = 1 only);
-  parity / parity_config / secondary / comm - see above and main().
+  parity / parity_config / secondary / droppath_ab / comm - see above and main().
+--dump-outputs DIR writes what the last timed step computed (losses, a seeded sample of every parameter gradient and their norms; see
+dump_outputs) as .npy files; inputs and weights are fixed by seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -114,6 +120,13 @@ def parse():
                          "gradients, ~25 GiB lower peak: room for every tower block's MLP pre-activation)")
     ap.add_argument("--dense-droppath", action="store_true",
                     help="evaluate dropped residual branches too and multiply them by 0 (the reference's schedule) instead of skipping them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: `comm` (N = 1: extra steps on a one-rank RCCL group), the in-run `parity` "
+                         "against the goldens, `secondary`, `droppath_ab`, `parity_config` / `other_precisions` and `cpu_baseline` (each still "
+                         "switched off by its --no-* flag).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the losses (float64) and a fixed, "
+                         "seeded sample of every parameter gradient (grad_sample.npy, float32) with each gradient's norm (grad_norm.npy, float64)")
     return ap.parse_args()
 
 
@@ -240,8 +253,7 @@ def measure_parity(model, dev):
     from mico_amd.model import MiCo, default_cfg
     from mico_amd.weights import synth_state_dict, synth_inputs
     from mico_amd.functional import l2_normalize
-    gd = os.path.join(ROOT, "tests", "golden")
-    load = lambda n: torch.load(os.path.join(gd, n), map_location="cpu", weights_only=False)
+    from tests.common import golden as load     # (joins the fixtures stored in pieces)
     rel = lambda a, r: ((a.detach().float().cpu() - r.float()).abs().max() / r.float().abs().max().clamp_min(1e-20)).item()
     out = {}
     was_training = model.training
@@ -314,6 +326,66 @@ def measure_parity(model, dev):
     out["metric"] = "max|out - ref| / max|ref| vs reference fp32 CPU outputs (tests/golden, generated by oracle/make_golden.py); losses relative"
     out["gate"] = 1e-3
     return out
+
+
+def build_model(cfg, seed=0, workers=8):
+    """MiCo(cfg) on the host with the synthetic weights loaded: the module and its state dict exactly as a serial
+    `MiCo(cfg)` + `synth_state_dict(..., seed)` + `load_state_dict` give them, in a fraction of the time.  The module is built in one
+    thread - the only consumer of torch's host generator meanwhile, so it draws what a serial build draws and the steps after it see the
+    same stochastic-depth and dropout draws - while the weights, each from its own (seed, name) generator, are synthesised by the
+    others; the shapes come from a build on the meta device, which draws nothing."""
+    from concurrent.futures import ThreadPoolExecutor
+    from mico_amd.model import MiCo
+    from mico_amd.weights import synth_state_dict
+    with torch.device("meta"):
+        shapes = {k: tuple(v.shape) for k, v in MiCo(cfg).state_dict().items()}
+    names = list(shapes)
+    chunks = [{n: shapes[n] for n in names[i::workers]} for i in range(workers)]
+    with ThreadPoolExecutor(1) as one, ThreadPoolExecutor(workers) as pool:
+        fut = one.submit(MiCo, cfg)
+        parts = list(pool.map(lambda c: synth_state_dict(c, seed, tie_lm_head=False), chunks))
+        model = fut.result()
+    merged = {}
+    for p in parts:
+        merged.update(p)
+    sd = {n: merged[n] for n in names if n in merged}
+    # the LM head's ties, as synth_state_dict makes them
+    w, d = "multimodal_encoder.bert.embeddings.word_embeddings.weight", "multimodal_encoder.cls.predictions.decoder.weight"
+    if w in sd and d in sd:
+        sd[d] = sd[w]
+    b, db = "multimodal_encoder.cls.predictions.bias", "multimodal_encoder.cls.predictions.decoder.bias"
+    if b in sd and db in sd:
+        sd[db] = sd[b]
+    model.load_state_dict(sd, strict=False)
+    return model, sd
+
+
+GRAD_SAMPLE = 4096     # gradient elements per parameter in grad_sample.npy
+
+
+def dump_outputs(path, model, losses):
+    """What the last timed step handed its caller: the losses and every parameter gradient.  The gradients (~1.2 G elements) are
+    represented by a fixed sample - GRAD_SAMPLE positions per parameter drawn by a generator seeded with 0, parameters in
+    named_parameters() order; a parameter without a gradient contributes zeros - and by each gradient's float64 norm: ~8 MB for ViT-g/14."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(float(v), dtype=np.float64))
+    g = torch.Generator().manual_seed(0)
+    samples, norms = [], []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        idx = torch.randint(n, (GRAD_SAMPLE,), generator=g) if n > GRAD_SAMPLE else torch.arange(n)
+        gr = p.grad
+        if gr is None:
+            samples.append(torch.zeros(len(idx), dtype=torch.float32))
+            norms.append(torch.zeros((), dtype=torch.float64))
+            continue
+        gr = gr.detach().reshape(-1)
+        samples.append(gr[idx.to(gr.device)].float())
+        norms.append(torch.linalg.vector_norm(gr, dtype=torch.float64))
+    np.save(os.path.join(path, "grad_sample.npy"), torch.cat([s.cpu() for s in samples]).numpy())
+    np.save(os.path.join(path, "grad_norm.npy"), torch.stack([t.cpu() for t in norms]).numpy())
 
 
 def relaunch_under_torchrun(args):
@@ -485,9 +557,7 @@ def main():
     from mico_amd.functional import DropPlan
     DropPlan.skip_dropped = not args.dense_droppath
     cfg = default_cfg(args.vision, vision_layers=args.layers)
-    model = MiCo(cfg)
-    sd_cpu = synth_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}, seed=0)
-    model.load_state_dict(sd_cpu, strict=False)
+    model, sd_cpu = build_model(cfg, seed=0)
     if args.no_bert_dropout:
         model.multimodal_encoder.bert.config.update(hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     model.to(dev)
@@ -607,6 +677,8 @@ def main():
     # ================= the headline measurement =================
     head, batch = measure(args.workload, args.task, b, args.steps, args.warmup, seed=1234, detail=args.gemm_detail)
     elapsed = head["ms_per_step"] * args.steps / 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, head["losses"])
 
     # ---- communication figures: exposed gradient-reduction wait per step, packed all-gather latency.  N > 1: from the timed steps.
     # N = 1: the SAME code on a one-rank RCCL group (mico_amd.distributed.force_dist: packed_all_gather's all_gather_into_tensor,
@@ -616,7 +688,7 @@ def main():
     forced_ms = None
     forced_peak = None
     exposed = sum(e0.elapsed_time(e1) for e0, e1 in finish_ms) / max(1, len(finish_ms)) if finish_ms else None
-    if world == 1 and not args.no_comm and rank == 0:
+    if args.full and world == 1 and not args.no_comm and rank == 0:
         from mico_amd import distributed as D
         try:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -640,7 +712,7 @@ def main():
             exposed = sum(e0.elapsed_time(e1) for e0, e1 in finish_ms) / max(1, len(finish_ms))
         except Exception as e:
             comm = {"error": repr(e)}
-    if (world > 1 or forced_ms is not None) and comm is None:
+    if args.full and (world > 1 or forced_ms is not None) and comm is None:
         feat = torch.randn(b, 512, device=dev)
         ids = batch["input_ids"]
         for _ in range(3):
@@ -743,7 +815,7 @@ def main():
     }
     if comm is not None:
         res["comm"] = comm
-    extras = not args.no_extras and args.workload in ("omni", "img_aud_txt") and not args.optimizer
+    extras = args.full and not args.no_extras and args.workload in ("omni", "img_aud_txt") and not args.optimizer
     if extras:
         # ---- the timed precision against the reference goldens, measured here and now ----
         del batch
@@ -856,7 +928,7 @@ def main():
         res["parity_config"] = others.pop(pc)
         if others:
             res["other_precisions"] = others
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(sd_cpu, args)
     sys.stdout.flush()
     # The complete record goes to stderr (and to MICO_BENCH_FULL, a path, when set: tools/profile_round.sh keeps it under profiles/); the ONE line on

@@ -21,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import ref_import  # noqa: E402
 from mico_amd.weights import synth_state_dict, synth_inputs  # noqa: E402
+from tests.common import save_golden  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 
@@ -70,7 +71,7 @@ def vit_fixture(vtype, depth, tag):
         grads={n: grad_digest(named[n].grad) for n in names if named[n].grad is not None},
         meta=dict(vtype=vtype, depth=depth, input_seed=77),
     )
-    torch.save(fx, os.path.join(OUT, f"vit_{tag}.pt"))
+    save_golden(fx, f"vit_{tag}.pt")        # > 1 MiB: stored in pieces, tests/common.golden joins them
     print("wrote", f"vit_{tag}.pt", tuple(out.shape), float(out.abs().max()))
     return m
 
@@ -109,7 +110,7 @@ def vit_bige_fixture(depth=2):
         grads={n: grad_digest(p.grad) for n, p in named.items() if p.grad is not None and not n.startswith("head.")},
         meta=dict(vtype="evaclip02_bige", depth=depth, input_seed=77),
     )
-    torch.save(fx, os.path.join(OUT, "vit_bige_d2.pt"))
+    save_golden(fx, "vit_bige_d2.pt")
     print("wrote vit_bige_d2.pt", tuple(out.shape), float(out.abs().max()), len(fx["grads"]), "gradient digests")
 
 

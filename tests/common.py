@@ -1,13 +1,42 @@
 import contextlib
+import glob
+import io
 import os
 
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# a fixture larger than this is stored as byte-exact consecutive pieces <name>.part0, .part1, ... (no committed file exceeds 1 MiB)
+GOLDEN_PART_BYTES = 1000 * 1024
 
 
 def golden(name):
-    return torch.load(os.path.join(GOLDEN, name), map_location="cpu", weights_only=False)
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return torch.load(path, map_location="cpu", weights_only=False)
+    parts = sorted(glob.glob(glob.escape(path) + ".part*"), key=lambda p: int(p.rsplit(".part", 1)[1]))
+    if not parts:
+        raise FileNotFoundError(path)
+    data = b"".join(open(p, "rb").read() for p in parts)
+    return torch.load(io.BytesIO(data), map_location="cpu", weights_only=False)
+
+
+def save_golden(obj, name):
+    """torch.save into tests/golden/<name>, split into GOLDEN_PART_BYTES pieces when larger (golden() joins them)."""
+    buf = io.BytesIO()
+    torch.save(obj, buf)
+    data = buf.getvalue()
+    path = os.path.join(GOLDEN, name)
+    for p in [path] + glob.glob(glob.escape(path) + ".part*"):
+        if os.path.exists(p):
+            os.remove(p)
+    if len(data) <= GOLDEN_PART_BYTES:
+        with open(path, "wb") as fh:
+            fh.write(data)
+        return
+    for i in range(0, len(data), GOLDEN_PART_BYTES):
+        with open(f"{path}.part{i // GOLDEN_PART_BYTES}", "wb") as fh:
+            fh.write(data[i:i + GOLDEN_PART_BYTES])
 
 
 def rel_err(a, b):

@@ -444,3 +444,29 @@ def test_bench_compact_line_keeps_the_contract():
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(line["cpu_baseline"]) and line["cpu_baseline"]["kind"] == "port"
     assert line["parity"]["worst"] == full["parity"]["worst"] < line["parity"]["gate"]
     assert "configs2_img_aud_txt_bf16" in line["secondary"]
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: the losses as float64 scalars, a fixed seeded sample of every parameter gradient as one float32 array
+    (zeros where a parameter has no gradient) and each gradient's float64 norm - the same files for the same gradients."""
+    import numpy as np
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(64, 96), torch.nn.Linear(96, 3), torch.nn.Linear(5, 5))   # the last one gets no gradient
+    m[1](m[0](torch.randn(8, 64))).square().sum().backward()
+    losses = {"loss_a": 1.25, "loss_b": 0.5}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, losses)
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert sorted(os.listdir(a)) == ["grad_norm.npy", "grad_sample.npy", "loss_a.npy", "loss_b.npy"]
+    assert np.load(a / "loss_a.npy").dtype == np.float64 and float(np.load(a / "loss_a.npy")) == 1.25
+    s, n = np.load(a / "grad_sample.npy"), np.load(a / "grad_norm.npy")
+    assert s.dtype == np.float32 and n.dtype == np.float64
+    params = list(m.parameters())
+    assert s.shape == (sum(min(p.numel(), bench.GRAD_SAMPLE) for p in params),) and n.shape == (len(params),)
+    assert np.array_equal(s, np.load(b / "grad_sample.npy")) and np.array_equal(n, np.load(b / "grad_norm.npy"))
+    for p, v in zip(params, n):
+        assert abs(v - (p.grad.double().norm().item() if p.grad is not None else 0.0)) <= 1e-9 * max(1.0, v)
+    g0 = m[0].weight.grad.reshape(-1)          # 6144 elements > GRAD_SAMPLE: the sample's values are elements of the gradient
+    assert np.isin(s[:bench.GRAD_SAMPLE], g0.numpy()).all()
+    assert not s[-(5 * 5 + 5):].any()          # the parameters without a gradient

@@ -320,6 +320,28 @@ int mico_rope(void* x, int64_t bs, int64_t rs, int B, int N, int H, int hd, cons
 int mico_im2row(const float* pixels, void* rows16, int B, int C, int H, int W, int P, int kpad, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Patch dropout (FLIP; transformer.py:144-185, eva_vit_model.py:620-631, rope.py:120-136).  keep: int32 [frames, nkeep] table of kept
+ * patch indices in [0, np), distinct per row, in the order the tokens take (token 1 + r of frame f is patch keep[f, r]; token 0 is CLS).
+ *  mico_im2row_keep:    mico_im2row of the kept patches only: rows16 [B * nkeep, kpad], row f * nkeep + r = patch keep[f, r] of frame f.
+ *  mico_patch_pos_keep: x fp32 [B * (1 + nkeep), cols] (row stride ld) after the bias-only patch GEMM (remap (nkeep, 1, 1)):
+ *                       x[f, 0] = cls + pos[0];  x[f, 1 + r] += pos[1 + keep[f, r]]   (pos fp32 [1 + np, cols]).
+ *  mico_rope_keep:      mico_rope where token 1 + n of frame b rotates with table row keep[fr, n], fr = frame_map[b] (compact frame
+ *                       list of a stochastic-depth branch) or b when frame_map is NULL; table_frames = rows of keep.  hd, strides % 8 == 0.
+ *  mico_pos_grad_keep:  dpos fp32 [1 + np, cols] = the positional-table gradient of a dropped pass:  dpos[0] = sum_f g[f, 0],
+ *                       dpos[1 + p] = sum over the frames that kept p of g[f, 1 + r(f, p)]; summed in frame order without atomics (bit-identical
+ *                       run to run).  inv_ws: int32 [B * np] workspace (the inverse map, -1 = dropped).  np <= 16384.
+ * Indices outside [0, np) never address memory (the element is zero / unchanged); validating the table is the caller's job.
+ * ------------------------------------------------------------------------------------------------------------- */
+int mico_im2row_keep(const float* pixels, void* rows16, const int* keep, int B, int C, int H, int W, int P, int kpad, int nkeep,
+                     int dtype, void* stream);
+int mico_patch_pos_keep(float* x, int64_t ld, const int* keep, int B, int nkeep, const float* cls, const float* pos, int np, int cols,
+                        void* stream);
+int mico_rope_keep(void* x, int64_t bs, int64_t rs, int B, int N, int H, int hd, const float* cos_t, const float* sin_t, const int* keep,
+                   int table_frames, const int* frame_map, int np, int inverse, int dtype, void* stream);
+int mico_pos_grad_keep(const float* g, int64_t ld, const int* keep, int B, int nkeep, int np, int cols, int* inv_ws, float* dpos,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Elementwise / data-movement helpers (all HBM-bound, 16-byte vectorised).
  * ------------------------------------------------------------------------------------------------------------- */
 /* dst16[r, 0:cols_pad] = T(scale * src32[r, 0:cols]) zero-padded; */

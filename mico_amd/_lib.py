@@ -79,6 +79,10 @@ PROTOTYPES = {
     "mico_attn_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.POINTER(AttnParams), c_int, c_vp],
     "mico_rope": [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
     "mico_im2row": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
+    "mico_im2row_keep": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
+    "mico_patch_pos_keep": [c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
+    "mico_rope_keep": [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp],
+    "mico_pos_grad_keep": [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp],
     "mico_cast_f32_to_16": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_f, c_int, c_vp],
     "mico_cast_16_to_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_f, c_int, c_int, c_vp],
     "mico_gather_rows_cast": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_int, c_f, c_vp, c_int,

@@ -862,3 +862,200 @@ extern "C" int mico_pool_video_bwd(const float* dpooled, float* dtokens, int64_t
     MICO_LAUNCH_CHECK();
     return MICO_OK;
 }
+
+// ======================================================================================================================
+// Patch dropout (FLIP; reference transformer.py:144-185, eva_vit_model.py:620-631, rope.py:120-136).  A training pass keeps `nkeep` of a
+// frame's np patches in the order of an int32 table keep[frame, r] (the host's draw: randn(frames, np).topk(nkeep).indices, unsorted).
+// Token row 1 + r of frame f is patch keep[f, r]; row 0 is CLS.  The host validates the table (mico_amd.functional.PatchKeep); an index
+// outside [0, np) that reaches a kernel anyway never addresses memory: the element it would produce is zero / left unchanged.
+// ======================================================================================================================
+namespace {
+
+// im2row of the kept patches: output row f * nkeep + r <- patch keep[f, r] of frame f.  8 elements (16 bytes) stored per work item.
+template <typename T>
+__global__ void im2row_keep_kernel(const float* __restrict__ px, T* __restrict__ rows16, const int* __restrict__ keep, int B, int C,
+                                   int H, int W, int P, int kpad, int nkeep) {
+    const int gw = W / P, np = (H / P) * gw;
+    const int k_real = C * P * P;
+    const int vpr = kpad >> 3;
+    const int64_t total = (int64_t)B * nkeep * vpr;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < total; i += (int64_t)gridDim.x * EB) {
+        const int64_t row = i / vpr;
+        const int k0 = (int)(i - row * vpr) * 8;
+        const int64_t b = row / nkeep;
+        const int pr = keep[row];
+        const bool ok = pr >= 0 && pr < np;
+        const int py = ok ? pr / gw : 0, pxx = ok ? pr - py * gw : 0;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = k0 + j;
+            if (ok && k < k_real) {
+                const int c = k / (P * P);
+                const int rem = k - c * P * P;
+                const int ii = rem / P, jj = rem - ii * P;
+                v[j] = px[((b * C + c) * H + py * P + ii) * W + pxx * P + jj];
+            } else {
+                v[j] = 0.f;
+            }
+        }
+        *(s16x8*)(rows16 + row * kpad + k0) = pack8<T>(v);
+    }
+}
+
+// Token rows of a dropped pass after the bias-only patch GEMM: row 0 of every frame = cls + pos[0]; row 1 + r += pos[1 + keep[f, r]].
+// 4 fp32 columns (16 bytes) per work item.
+__global__ void patch_pos_keep_kernel(float* __restrict__ x, int64_t ld, const int* __restrict__ keep, int B, int nkeep,
+                                      const float* __restrict__ cls, const float* __restrict__ pos, int np, int cols) {
+    const int cv = cols >> 2, ntok = nkeep + 1;
+    const int64_t total = (int64_t)B * ntok * cv;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < total; i += (int64_t)gridDim.x * EB) {
+        const int64_t row = i / cv;
+        const int c = (int)(i - row * cv) * 4;
+        const int64_t f = row / ntok;
+        const int t = (int)(row - f * ntok);
+        f32x4* px = (f32x4*)(x + row * ld + c);
+        if (t == 0) {
+            *px = *(const f32x4*)(cls + c) + *(const f32x4*)(pos + c);
+        } else {
+            const int p = keep[f * nkeep + t - 1];
+            if (p >= 0 && p < np) *px = *px + *(const f32x4*)(pos + (int64_t)(1 + p) * cols + c);
+        }
+    }
+}
+
+// rope_kernel with a per-frame table row: token 1 + n of (compact) frame b rotates with table row keep[fr, n], fr = frame_map[b] (or b).
+// 8 elements (16 bytes) per work item.
+template <typename T>
+__global__ void rope_keep_kernel(T* __restrict__ x, int64_t bs, int64_t rs, int B, int N, int H, int hd, const float* __restrict__ cos_t,
+                                 const float* __restrict__ sin_t, const int* __restrict__ keep, int table_frames,
+                                 const int* __restrict__ frame_map, int np, int inverse) {
+    const int hv = hd >> 3, nk = N - 1;
+    const int64_t total = (int64_t)B * nk * H * hv;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < total; i += (int64_t)gridDim.x * EB) {
+        int64_t t = i;
+        const int d0 = (int)(t % hv) * 8; t /= hv;
+        const int h = (int)(t % H); t /= H;
+        const int n = (int)(t % nk); t /= nk;
+        const int64_t b = t;
+        const int64_t fr = frame_map ? frame_map[b] : b;
+        if (fr < 0 || fr >= table_frames) continue;
+        const int tr = keep[fr * nk + n];
+        if (tr < 0 || tr >= np) continue;
+        T* p = x + b * bs + (int64_t)(n + 1) * rs + h * hd + d0;
+        float v[8], o[8];
+        unpack8<T>(*(const s16x8*)p, v);
+        const float* cp = cos_t + (int64_t)tr * hd + d0;
+        const float* sp = sin_t + (int64_t)tr * hd + d0;
+        const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
+        const f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
+        const float c[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+        const float s[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            if (!inverse) {   // y = x cos + rotate_half(x) sin ; rotate_half: (x0, x1) -> (-x1, x0)
+                o[j] = v[j] * c[j] - v[j + 1] * s[j];
+                o[j + 1] = v[j + 1] * c[j + 1] + v[j] * s[j + 1];
+            } else {          // transpose of the above (gradient)
+                o[j] = v[j] * c[j] + v[j + 1] * s[j + 1];
+                o[j + 1] = v[j + 1] * c[j + 1] - v[j] * s[j];
+            }
+        }
+        *(s16x8*)p = pack8<T>(o);
+    }
+}
+
+// inverse keep map of one frame per workgroup, built in LDS: inv[f, p] = r where keep[f, r] == p, -1 where patch p was dropped.
+__global__ void keep_inverse_kernel(const int* __restrict__ keep, int nkeep, int np, int* __restrict__ inv) {
+    extern __shared__ int s_inv[];
+    const int64_t f = blockIdx.x;
+    for (int p = threadIdx.x; p < np; p += blockDim.x) s_inv[p] = -1;
+    __syncthreads();
+    for (int r = threadIdx.x; r < nkeep; r += blockDim.x) {
+        const int p = keep[f * nkeep + r];
+        if (p >= 0 && p < np) s_inv[p] = r;
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < np; p += blockDim.x) inv[f * np + p] = s_inv[p];
+}
+
+// dpos[p, c] = sum over frames f, in frame order, of g[f, tok(f, p), c]: tok(f, 0) = 0 (CLS), tok(f, 1 + q) = 1 + inv[f, q] (frames that
+// dropped patch q contribute nothing).  No atomics: one lane owns 4 columns of one table row; 8 frames' loads in flight, summed in order.
+constexpr int PGB = 64;
+__global__ __launch_bounds__(PGB) void pos_grad_keep_kernel(const float* __restrict__ g, int64_t ld, const int* __restrict__ inv, int B,
+                                                            int nkeep, int np, int cols, float* __restrict__ dpos) {
+    const int c = (blockIdx.x * PGB + threadIdx.x) * 4;
+    const int p = blockIdx.y;
+    if (c >= cols) return;
+    const int64_t ntok = nkeep + 1;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int f0 = 0; f0 < B; f0 += 8) {
+        f32x4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int f = f0 + j;
+            const int r = (f < B) ? (p == 0 ? 0 : 1 + inv[(int64_t)f * np + p - 1]) : -1;     // token row, 0 = dropped for p > 0
+            const bool hit = f < B && (p == 0 || r > 0);
+            v[j] = hit ? *(const f32x4*)(g + ((int64_t)f * ntok + r) * ld + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+    }
+    *(f32x4*)(dpos + (int64_t)p * cols + c) = s;
+}
+
+}  // namespace
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int mico_im2row_keep(const float* pixels, void* rows16, const int* keep, int B, int C, int H, int W, int P, int kpad,
+                                int nkeep, int dtype, void* stream) {
+    MICO_CHECK(dtype_ok(dtype) && pixels && rows16 && keep, "mico_im2row_keep: bad args");
+    MICO_CHECK(P > 0 && H % P == 0 && W % P == 0, "mico_im2row_keep: image %dx%d is not a multiple of the patch size %d", H, W, P);
+    MICO_CHECK(kpad % 8 == 0 && kpad >= C * P * P && aligned16(rows16), "mico_im2row_keep: kpad must be a multiple of 8 and >= C*P*P, rows 16-byte aligned");
+    MICO_CHECK(nkeep >= 1 && nkeep <= (H / P) * (W / P), "mico_im2row_keep: keep count %d outside [1, %d]", nkeep, (H / P) * (W / P));
+    if (B <= 0) return MICO_OK;
+    const int64_t total = (int64_t)B * nkeep * (kpad / 8);
+    DISPATCH_T16(dtype, MICO_LAUNCH(im2row_keep_kernel<T>, dim3(egrid(total)), dim3(EB), 0, ST, pixels, (T*)rows16, keep, B, C, H, W, P, kpad, nkeep));
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_patch_pos_keep(float* x, int64_t ld, const int* keep, int B, int nkeep, const float* cls, const float* pos, int np,
+                                   int cols, void* stream) {
+    MICO_CHECK(x && keep && cls && pos && cols > 0 && nkeep >= 1 && nkeep <= np, "mico_patch_pos_keep: bad args");
+    MICO_CHECK(cols % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(cls) && aligned16(pos), "mico_patch_pos_keep: needs 16-byte rows");
+    if (B <= 0) return MICO_OK;
+    MICO_LAUNCH(patch_pos_keep_kernel, dim3(egrid((int64_t)B * (nkeep + 1) * (cols / 4))), dim3(EB), 0, ST, x, ld, keep, B, nkeep, cls, pos, np, cols);
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_rope_keep(void* x, int64_t bs, int64_t rs, int B, int N, int H, int hd, const float* cos_t, const float* sin_t,
+                              const int* keep, int table_frames, const int* frame_map, int np, int inverse, int dtype, void* stream) {
+    MICO_CHECK(dtype_ok(dtype) && x && cos_t && sin_t && keep, "mico_rope_keep: bad args");
+    MICO_CHECK(hd % 8 == 0 && rs % 8 == 0 && bs % 8 == 0 && aligned16(x) && aligned16(cos_t) && aligned16(sin_t),
+               "mico_rope_keep: hd and strides must be multiples of 8, pointers 16-byte aligned");
+    MICO_CHECK(N - 1 <= np, "mico_rope_keep: %d kept tokens for a %d-row table", N - 1, np);
+    if (B <= 0 || N <= 1) return MICO_OK;
+    MICO_CHECK(frame_map != nullptr || B <= table_frames, "mico_rope_keep: %d frames for a %d-frame keep table", B, table_frames);
+    const int64_t total = (int64_t)B * (N - 1) * H * (hd / 8);
+    DISPATCH_T16(dtype, MICO_LAUNCH(rope_keep_kernel<T>, dim3(egrid(total)), dim3(EB), 0, ST, (T*)x, bs, rs, B, N, H, hd, cos_t, sin_t, keep,
+                                    table_frames, frame_map, np, inverse));
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_pos_grad_keep(const float* g, int64_t ld, const int* keep, int B, int nkeep, int np, int cols, int* inv_ws,
+                                  float* dpos, void* stream) {
+    MICO_CHECK(g && keep && inv_ws && dpos && cols > 0 && nkeep >= 1 && nkeep <= np, "mico_pos_grad_keep: bad args");
+    MICO_CHECK(cols % 4 == 0 && ld % 4 == 0 && aligned16(g) && aligned16(dpos), "mico_pos_grad_keep: needs 16-byte rows");
+    MICO_CHECK((int64_t)np * 4 <= 65536, "mico_pos_grad_keep: %d patches exceed the LDS inverse map", np);
+    if (B > 0) {
+        MICO_LAUNCH(keep_inverse_kernel, dim3(B), dim3(256), np * sizeof(int), ST, keep, nkeep, np, inv_ws);
+        MICO_LAUNCH_CHECK();
+    }
+    MICO_LAUNCH(pos_grad_keep_kernel, dim3((cols / 4 + PGB - 1) / PGB, np + 1), dim3(PGB), 0, ST, g, ld, inv_ws, B, nkeep, np, cols, dpos);
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}

@@ -480,6 +480,47 @@ class DropPlan:
         return sum(self.counts) / float(len(self.counts) * self.n_frames)
 
 
+def patch_keep_count(np_, prob):
+    """Patches a frame keeps under patch dropout at rate prob (transformer.py:171-172): max(1, int(np * (1 - prob)))."""
+    return max(1, int(np_ * (1.0 - prob)))
+
+
+def check_patch_keep(table, n_frames, np_, width):
+    """Host-side validation of a patch-dropout table (a draw or an injected one): integer [n_frames, width], every index in [0, np_), no
+    index twice in a row.  Raises ValueError; returns the table as a CPU int64 tensor."""
+    t = torch.as_tensor(table).detach()
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"patch_keep must be an integer table, got {t.dtype}")
+    t = t.to("cpu", torch.int64)
+    if t.dim() != 2 or t.shape[0] != n_frames:
+        raise ValueError(f"patch_keep must be [{n_frames} frames, {width}], got {tuple(t.shape)}")
+    if t.shape[1] != width:
+        raise ValueError(f"patch_keep has {t.shape[1]} kept patches per frame; this tower keeps {width} of {np_}")
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= np_):
+        raise ValueError(f"patch_keep holds an index outside [0, {np_})")
+    if width > 1 and bool((t.sort(dim=1).values.diff(dim=1) == 0).any()):
+        raise ValueError("patch_keep repeats a patch index within a frame")
+    return t
+
+
+class PatchKeep:
+    """One tower pass's patch dropout (FLIP; transformer.py:144-185, eva_vit_model.py:620-631): the frames keep k of their np patches,
+    token 1 + r of frame f being patch host[f, r] (CLS stays row 0), so the pass runs at N = 1 + k tokens per frame instead of
+    TowerSpec.N.  The table is validated on the host (check_patch_keep) and reaches the device the way DropPlan's do: pinned, no sync."""
+    __slots__ = ("host", "dev", "k", "N", "np")
+
+    def __init__(self, table, n_frames, np_, width, dev):
+        self.host = check_patch_keep(table, n_frames, np_, width)
+        self.k, self.N, self.np = width, width + 1, np_
+        self.dev = _h2d(self.host.to(torch.int32), dev)
+
+    def slice(self, c0, c1):
+        """The frames [c0, c1) (a chunk of the pass): the device table is a view, nothing is copied."""
+        out = object.__new__(PatchKeep)
+        out.host, out.dev, out.k, out.N, out.np = self.host[c0:c1], self.dev[c0:c1], self.k, self.N, self.np
+        return out
+
+
 _TAIL_EXP = None   # experiment hook (tools/precision_probe.py --tail)
 
 
@@ -570,18 +611,21 @@ def _postnorm_block_backward(spec, P, G, b, a, g, Bf, dt, dev, strides3, S):
     _gemm_dx(dqkv, [P(b + "attn.qkv.weight")], "qkv", g, ln=False, alpha=inv_s, resid=g)
 
 
-def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None):
+def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None, keep=None):
     """One pass of the tower over the frames in `groups`.  save=False keeps nothing for a backward (chunked forward).
     diet (plain-MLP towers): 1 = the MLP intermediates are not kept (the backward recomputes fc1 + GELU / GELU'), 2 = nor the LayerNorm
-    outputs (recomputed from the saved fp32 rows) - see runtime.set_activation_diet."""
+    outputs (recomputed from the saved fp32 rows) - see runtime.set_activation_diet.
+    keep (PatchKeep): patch dropout - the pass runs at keep.N tokens per frame (only the kept patches are embedded)."""
     dt = runtime.compute_dtype()
     P = lambda n: params[spec.idx[n]]
     dev = params[0].device
-    D, N, np_, H, hd = spec.D, spec.N, spec.np, spec.H, spec.hd
+    D, N, np_, H, hd = spec.D, spec.N if keep is None else keep.N, spec.np, spec.H, spec.hd
     arch = spec.arch
     depth = arch["depth_built"]
     Bf = sum(g.shape[0] for g in groups)
     M = Bf * N
+    if keep is not None and arch.get("postnorm"):
+        raise NotImplementedError("patch dropout is not implemented for the post-norm tower (EVA02-CLIP-bigE-14-plus)")
     if arch.get("postnorm"):
         plan, diet = None, 0          # (the post-norm tower evaluates every branch and scales it: no frame compaction, no diet)
         if dp_scale is not None:
@@ -595,21 +639,30 @@ def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None):
     x = _empty((M, D), torch.float32, dev)
     # ---- patch embedding: im2row + GEMM(+bias +pos, patch rows -> token rows) ; CLS rows ----
     pe_w, pe_b, pos = P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed")
-    pos2 = pos.detach().reshape(N, D)
+    pos2 = pos.detach().reshape(spec.N, D)
     saved_rows = []
     f0 = 0
     for g in groups:
         C = g.shape[1]
         kpad = spec.kpad3 if C == 3 else spec.kpad1
         w16, ks = runtime.gemm_weight([pe_w], "pe3" if C == 3 else "pe1", k_pad=kpad, channel_sum=(C != 3))
-        rows16 = _empty((g.shape[0] * np_, kpad), dt, dev)
-        ops.im2row(g.contiguous().float(), rows16, spec.P, kpad)
-        ops.gemm(rows16, w16, x[f0 * N:], M=g.shape[0] * np_, N=D, K=kpad, bias=pe_b, pos=pos2, pos_rows=N,
-                 remap=(np_, 1, 1), ksegs=ks)
+        if keep is None:
+            rows16 = _empty((g.shape[0] * np_, kpad), dt, dev)
+            ops.im2row(g.contiguous().float(), rows16, spec.P, kpad)
+            ops.gemm(rows16, w16, x[f0 * N:], M=g.shape[0] * np_, N=D, K=kpad, bias=pe_b, pos=pos2, pos_rows=N,
+                     remap=(np_, 1, 1), ksegs=ks)
+        else:
+            # patch dropout: the kept patches only, bias-only epilogue; their position rows (gathered per frame) and the CLS rows follow
+            rows16 = _empty((g.shape[0] * keep.k, kpad), dt, dev)
+            ops.im2row_keep(g.contiguous().float(), rows16, keep.dev[f0:f0 + g.shape[0]], spec.P, kpad)
+            ops.gemm(rows16, w16, x[f0 * N:], M=g.shape[0] * keep.k, N=D, K=kpad, bias=pe_b, remap=(keep.k, 1, 1), ksegs=ks)
         if save:
             saved_rows.append(rows16)
         f0 += g.shape[0]
-    ops.cls_rows(x, Bf, N, P("cls_token").detach().reshape(D), pos2[0])
+    if keep is None:
+        ops.cls_rows(x, Bf, N, P("cls_token").detach().reshape(D), pos2[0])
+    else:
+        ops.patch_pos_keep(x, keep.dev, P("cls_token").detach().reshape(D), pos2)
 
     def branch_io(i, which):
         """-> (kept frames, frame list | None, scale vector | None)"""
@@ -647,7 +700,10 @@ def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None):
             qkv_bias = torch.cat((qb, torch.zeros_like(qb), vb))
             qkv = _empty((M1, 3 * D), dt, dev)
             _gemm_fwd(ln1b, D, _qkv_params(P, b, arch), "qkv", qkv, bias=qkv_bias)
-            if spec.rope is not None:
+            if spec.rope is not None and keep is not None:      # each kept token rotates with its own patch's table row (rope.py:120-136)
+                ops.rope_keep(qkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1)
+                ops.rope_keep(qkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1)
+            elif spec.rope is not None:
                 ops.rope(qkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1])
                 ops.rope(qkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1])
             ao = _empty((M1, D), dt, dev)
@@ -734,7 +790,7 @@ def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None):
     saved = None
     if save:
         saved = dict(acts=acts, dt=dt, final=(x, mean_n, rstd_n), groups_meta=[(g.shape[0], g.shape[1]) for g in groups],
-                     saved_rows=saved_rows, Bf=Bf)
+                     saved_rows=saved_rows, Bf=Bf, keep=keep)
     return out.view(Bf, N, D), saved
 
 
@@ -746,7 +802,8 @@ def _tower_backward(spec, params, saved, dout, grads, final=True):
     dt = saved["dt"]
     P = lambda n: params[spec.idx[n]]
     dev = dout.device
-    D, N, np_, H, hd, Bf = spec.D, spec.N, spec.np, spec.H, spec.hd, saved["Bf"]
+    keep = saved.get("keep")
+    D, N, np_, H, hd, Bf = spec.D, spec.N if keep is None else keep.N, spec.np, spec.H, spec.hd, saved["Bf"]
     arch = spec.arch
     M = Bf * N
     S = runtime.grad_scale()
@@ -914,7 +971,10 @@ def _tower_backward(spec, params, saved, dout, grads, final=True):
             delta = _empty((B1, H, N), torch.float32, dev)
             ops.attn_bwd(qkv, qkv[:, D:], qkv[:, 2 * D:], a["ao"], dao, a["lse"], dqkv, dqkv[:, D:], dqkv[:, 2 * D:], delta,
                          B=B1, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **strides3)
-            if spec.rope is not None:
+            if spec.rope is not None and keep is not None:
+                ops.rope_keep(dqkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1, inverse=True)
+                ops.rope_keep(dqkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1, inverse=True)
+            elif spec.rope is not None:
                 ops.rope(dqkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], inverse=True)
                 ops.rope(dqkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], inverse=True)
             dbias = torch.zeros(3 * D, dtype=torch.float32, device=dev)      # filled by the qkv weight-gradient launch below
@@ -946,16 +1006,20 @@ def _tower_backward(spec, params, saved, dout, grads, final=True):
             hook(grads.span(i0, i1), params[i0:i1])
     runtime.restore(pstate)
     # ---------------- patch embedding ----------------
-    dpos = torch.zeros(N * D, dtype=torch.float32, device=dev)
-    ops.colsum(g, dpos, rows=Bf, cols=N * D, ld=N * D)
-    G("pos_embed").add_(dpos.view(1, N, D))
+    if keep is None:
+        dpos = torch.zeros(N * D, dtype=torch.float32, device=dev)
+        ops.colsum(g, dpos, rows=Bf, cols=N * D, ld=N * D)
+    else:     # patch dropout: each token's gradient lands on its own patch's table row (fixed-order sum over the frames, no atomics)
+        dpos = ops.pos_grad_keep(g, keep.dev, np_).view(-1)
+    G("pos_embed").add_(dpos.view(1, spec.N, D))
     G("cls_token").add_(dpos[:D].view(1, 1, D))
     pe_w = P("patch_embed.proj.weight")
     PP = spec.P * spec.P
     f0 = 0
     for (nf, C), rows16 in zip(saved["groups_meta"], saved["saved_rows"]):
-        gp16 = _empty((nf * np_, D), dt, dev)
-        ops.gather_rows_cast(g[f0 * N:], gp16, remap=(np_, 1, 1), scale=S)
+        rows_pe = np_ if keep is None else keep.k
+        gp16 = _empty((nf * rows_pe, D), dt, dev)
+        ops.gather_rows_cast(g[f0 * N:], gp16, remap=(rows_pe, 1, 1), scale=S)
         kpad = rows16.shape[1]
         dw = torch.zeros((D, kpad), dtype=torch.float32, device=dev)
         linear_wgrad(gp16, rows16, dw, inv_s)
@@ -990,7 +1054,7 @@ _SOFT_FRAC = float(os.environ.get("MICO_HBM_SOFT_FRAC", "0.87"))
 _MLP_KEEP_MARGIN = int(float(os.environ.get("MICO_MLP_KEEP_MARGIN_GIB", "6")) * (1 << 30))
 
 
-def tower_plan(spec, n_frames, device, kept=1.0, block_tokens=None):
+def tower_plan(spec, n_frames, device, kept=1.0, block_tokens=None, n_tok=None):
     """-> (frames per tower pass, TowerDiet).  Saved activations of the pre-norm plain-MLP tower cost, per kept token and block: two LayerNorm
     input copies (fp32: 8 D bytes; as fp16 normalised rows, TowerDiet.xh16: 4 D), the two LayerNorm outputs 4 D, qkv 6 D, the attention output
     2 D, the two MLP intermediates 4 hidden - depth * N * (20 D + 4 hidden) = 542 MB per frame for ViT-g/14 when everything is kept.  When the
@@ -1006,11 +1070,12 @@ def tower_plan(spec, n_frames, device, kept=1.0, block_tokens=None):
     intermediates of ~10 of the 40 blocks kept (round 3: level 2, 166 GB of activations; round 2: three chunks, +0.67).
     kept: fraction of the (block, branch, frame) triples the step's stochastic-depth draw keeps (only those are evaluated and saved);
     block_tokens (optional, per block): kept MLP-branch tokens of each block (DropPlan counts x N) - prices the per-block MLP choice exactly.
+    n_tok: tokens per frame of the pass (patch dropout: 1 + kept patches; default TowerSpec.N).
     The post-norm tower (bigE) and the SwiGLU towers keep everything (no diet): only chunks are priced for them, at their own bytes per frame."""
     if torch.device(device).type != "cuda":
         from ._lib import MicoHipError
         raise MicoHipError("the ViT tower runs on an MI355X device only (parameters are on %s): mico_amd has no CPU path" % device)
-    depth, N, D, Hd = spec.arch["depth_built"], spec.N, spec.D, spec.hidden
+    depth, N, D, Hd = spec.arch["depth_built"], n_tok or spec.N, spec.D, spec.hidden
     postnorm = bool(spec.arch.get("postnorm"))
     dietable = not spec.arch["swiglu"] and not postnorm
     # (the post-norm block saves fp32 br1 / br2 (8 D), x16a / x16b / ao (6 D), qkv (6 D), act + h (4 hidden): the same 20 D + 4 hidden per token)
@@ -1121,37 +1186,40 @@ def tower_plan(spec, n_frames, device, kept=1.0, block_tokens=None):
     return best[1], TowerDiet(depth, best[2], keep=best[3] if best[2] == 3 else None, mlp_pre=best[4] if best[2] == 3 else False)
 
 
-def tower_chunk_frames(spec, n_frames, device):
+def tower_chunk_frames(spec, n_frames, device, n_tok=None):
     """Frames per tower pass (see tower_plan)."""
-    return tower_plan(spec, n_frames, device)[0]
+    return tower_plan(spec, n_frames, device, n_tok=n_tok)[0]
 
 
 class EvaTowerFn(torch.autograd.Function):
     _logged_plan = None
 
     @staticmethod
-    def forward(ctx, spec, groups, dp_scale, *params):
+    def forward(ctx, spec, groups, dp_scale, keep, *params):
+        """keep: PatchKeep of the pass (patch dropout) or None."""
         runtime.remember_precision(ctx)
         with runtime.using(runtime.snapshot()):   # the block loop switches the state per block (runtime.enter_block)
-            return EvaTowerFn._forward(ctx, spec, groups, dp_scale, *params)
+            return EvaTowerFn._forward(ctx, spec, groups, dp_scale, keep, *params)
 
     @staticmethod
-    def _forward(ctx, spec, groups, dp_scale, *params):
+    def _forward(ctx, spec, groups, dp_scale, keep, *params):
         Bf = sum(g.shape[0] for g in groups)
+        n_tok = spec.N if keep is None else keep.N
         needs_grad = any(ctx.needs_input_grad)    # False under torch.no_grad(): nothing is kept for a backward then
         depth = spec.arch["depth_built"]
         plan, chunk, diet = None, Bf, TowerDiet(depth, 0)
         if needs_grad:
             plan = DropPlan(dp_scale, Bf, params[0].device) if dp_scale is not None else None
             kept = plan.kept_fraction() if plan is not None else 1.0
-            btok = [plan.counts[2 * i + 1] * spec.N for i in range(depth)] if (plan is not None and len(plan.counts) == 2 * depth) else None
-            chunk, diet = tower_plan(spec, Bf, params[0].device, kept, btok)
+            btok = [plan.counts[2 * i + 1] * n_tok for i in range(depth)] if (plan is not None and len(plan.counts) == 2 * depth) else None
+            chunk, diet = tower_plan(spec, Bf, params[0].device, kept, btok, n_tok=n_tok)
 
             def record(**more):
                 runtime.last_tower_plan = dict(frames=Bf, frames_per_pass=min(chunk, Bf), diet=diet.level, mlp_blocks_kept=diet.mlp_blocks,
                                                mlp_blocks=_ranges([i for i, k in enumerate(diet.keep_mlp) if k]) if diet.level == 3 else None,
                                                rows_fp16_normalised=diet.xh16, kept_fraction=kept,
-                                               mlp_stash=("pre-activation (2 B per hidden unit)" if diet.mlp_pre else "gelu + gelu' (4 B per hidden unit)"), **more)
+                                               mlp_stash=("pre-activation (2 B per hidden unit)" if diet.mlp_pre else "gelu + gelu' (4 B per hidden unit)"),
+                                               tokens_per_frame=n_tok, **more)
             record()
             if (Bf, min(chunk, Bf), diet.level, tuple(diet.keep_mlp)) != EvaTowerFn._logged_plan:   # once per distinct plan and process (= rank)
                 EvaTowerFn._logged_plan = (Bf, min(chunk, Bf), diet.level, tuple(diet.keep_mlp))
@@ -1160,7 +1228,7 @@ class EvaTowerFn(torch.autograd.Function):
         if chunk >= Bf:
             retry = False
             try:
-                out, ctx.saved = _tower_forward(spec, groups, dp_scale, params, save=needs_grad, diet=diet, plan=plan)
+                out, ctx.saved = _tower_forward(spec, groups, dp_scale, params, save=needs_grad, diet=diet, plan=plan, keep=keep)
                 ctx.chunked = None
                 return out
             except torch.cuda.OutOfMemoryError:
@@ -1189,7 +1257,7 @@ class EvaTowerFn(torch.autograd.Function):
                 _log.warning("tower pass ran out of memory: retrying with %d frames per pass, activation diet %s (rank-local decision)",
                              min(chunk, Bf), diet.describe())
                 if chunk >= Bf:
-                    out, ctx.saved = _tower_forward(spec, groups, dp_scale, params, save=needs_grad, diet=diet, plan=plan)
+                    out, ctx.saved = _tower_forward(spec, groups, dp_scale, params, save=needs_grad, diet=diet, plan=plan, keep=keep)
                     ctx.chunked = None
                     return out
         if plan is not None:      # the chunks draw their own plans from their slices of dp_scale: this one only priced the step
@@ -1201,12 +1269,13 @@ class EvaTowerFn(torch.autograd.Function):
         for c0 in starts:
             c1 = min(Bf, c0 + chunk)
             sub_dp = dp_scale[:, :, c0:c1].contiguous() if dp_scale is not None else None
-            keep = c0 == starts[-1]      # the last chunk's activations fit by construction: keep them, the backward starts there
-            o, saved = _tower_forward(spec, _slice_groups(groups, c0, c1), sub_dp, params, save=keep, diet=diet)
-            if keep:
+            last = c0 == starts[-1]      # the last chunk's activations fit by construction: keep them, the backward starts there
+            o, saved = _tower_forward(spec, _slice_groups(groups, c0, c1), sub_dp, params, save=last, diet=diet,
+                                      keep=keep.slice(c0, c1) if keep is not None else None)
+            if last:
                 ctx.saved = saved
             outs.append(o)
-        ctx.chunked = (groups, dp_scale, chunk, Bf)
+        ctx.chunked = (groups, dp_scale, chunk, Bf, keep)
         return torch.cat(outs, dim=0)
 
     @staticmethod
@@ -1220,7 +1289,7 @@ class EvaTowerFn(torch.autograd.Function):
             ctx.saved = None
             runtime.mem_trace("tower backward end")
         else:
-            groups, dp_scale, chunk, Bf = ctx.chunked
+            groups, dp_scale, chunk, Bf, keep = ctx.chunked
             starts = list(range(0, Bf, chunk))
             for c0 in reversed(starts):      # last chunk first: its activations were kept by the forward, the others are recomputed
                 c1 = min(Bf, c0 + chunk)
@@ -1228,10 +1297,11 @@ class EvaTowerFn(torch.autograd.Function):
                     saved, ctx.saved = ctx.saved, None
                 else:
                     sub_dp = dp_scale[:, :, c0:c1].contiguous() if dp_scale is not None else None
-                    _, saved = _tower_forward(spec, _slice_groups(groups, c0, c1), sub_dp, params, save=True, diet=ctx.diet)
+                    _, saved = _tower_forward(spec, _slice_groups(groups, c0, c1), sub_dp, params, save=True, diet=ctx.diet,
+                                              keep=keep.slice(c0, c1) if keep is not None else None)
                 _tower_backward(spec, params, saved, dout[c0:c1], grads, final=(c0 == starts[0]))
                 del saved
-        return (None, None, None) + grads.result()
+        return (None, None, None, None) + grads.result()
 
 
 # ======================================================================================================================

@@ -91,12 +91,41 @@ class _PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(3, embed_dim, kernel_size=patch_size, stride=patch_size)
 
 
+class PatchDropout(nn.Module):
+    """transformer.py:144-185 (FLIP, https://arxiv.org/abs/2212.00794): in training mode each frame keeps a random
+    max(1, int(np * (1 - prob))) of its np patch tokens, drawn right after the position embedding; the CLS token always stays.
+    Parameter-free.  The tower applies it itself (EVAVisionTransformer.forward_groups draws the table, functional.EvaTowerFn runs the
+    pass at 1 + keep tokens per frame): this module holds the rate and the draw, it does not transform a token tensor."""
+
+    def __init__(self, prob, exclude_first_token=True):
+        super().__init__()
+        assert 0 <= prob < 1.
+        assert exclude_first_token, "the EVA towers keep their CLS token (exclude_first_token=True)"
+        self.prob = prob
+        self.exclude_first_token = exclude_first_token
+
+    def keep_count(self, num_patches):
+        return Fn.patch_keep_count(num_patches, self.prob)
+
+    def draw(self, n_frames, num_patches):
+        """The reference's draw (transformer.py:174-175) on torch's default CPU generator: randn(frames, np).topk(keep).indices -
+        kept patch indices per frame, in topk order (not sorted).  int64 [n_frames, keep] host tensor."""
+        rand = torch.randn(n_frames, num_patches, device="cpu")
+        return rand.topk(self.keep_count(num_patches), dim=-1).indices
+
+    def forward(self, x):
+        raise RuntimeError("PatchDropout is applied inside the EVA tower pass (EVAVisionTransformer.forward_groups); it has no tensor forward")
+
+    def extra_repr(self):
+        return f"prob={self.prob}"
+
+
 class EVAVisionTransformer(nn.Module):
     """Parameter layout and forward surface of eva_vit_model.py:488-659 (use_mean_pooling=False, no rel-pos bias, no layer
     scale - the only configuration the MiCo JSON configs select)."""
 
     def __init__(self, img_size=224, patch_size=16, num_classes=512, embed_dim=768, depth=12, num_heads=12,
-                 mlp_ratio=4.0, drop_path_rate=0.0, rope=False, naiveswiglu=False, subln=False, postnorm=False):
+                 mlp_ratio=4.0, drop_path_rate=0.0, rope=False, naiveswiglu=False, subln=False, postnorm=False, patch_dropout=0.):
         super().__init__()
         assert not (postnorm and (naiveswiglu or subln or rope)), "the post-norm block is built for the plain-MLP tower (EVA02-CLIP-bigE-14-plus)"
         self.postnorm = bool(postnorm)
@@ -114,6 +143,8 @@ class EVAVisionTransformer(nn.Module):
         self.blocks = nn.ModuleList([_Block(embed_dim, hidden, subln, naiveswiglu, dpr[i]) for i in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
         self.head = nn.Linear(embed_dim, num_classes)
+        # eva_vit_model.py:561: a rate of 0 is the identity (no draw, no table: the pass is today's full-length one)
+        self.patch_dropout = PatchDropout(patch_dropout) if patch_dropout > 0. else nn.Identity()
         self.mlp_hidden = hidden
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         nn.init.trunc_normal_(self.cls_token, std=0.02)
@@ -158,18 +189,39 @@ class EVAVisionTransformer(nn.Module):
         mask = torch.bernoulli(keep.expand(len(probs), 2, n_frames))
         return (mask / keep).contiguous()
 
-    def forward_groups(self, groups, drop_path_scale=None):
+    def patch_dropout_active(self):
+        """Patch dropout applies exactly when the reference applies it (eva_vit_model.py:621-622): training mode and a rate > 0."""
+        return self.training and isinstance(self.patch_dropout, PatchDropout) and self.patch_dropout.prob > 0.
+
+    def _patch_keep(self, n_frames, device, injected=None):
+        """-> functional.PatchKeep of this pass, or None when patch dropout is inactive.  The table is drawn on the HOST like the DropPath
+        multipliers (one draw over all frames of the call) or injected (parity tests); either way it is validated there."""
+        np_ = self.patch_embed.num_patches
+        if injected is not None and not isinstance(self.patch_dropout, PatchDropout):
+            raise ValueError("patch_keep was given but this tower has no patch dropout (patch_dropout=0)")
+        if not self.patch_dropout_active():
+            return None
+        if self.postnorm:
+            raise NotImplementedError("patch dropout is not implemented for the post-norm tower (EVA02-CLIP-bigE-14-plus)")
+        table = injected if injected is not None else self.patch_dropout.draw(n_frames, np_)
+        return Fn.PatchKeep(table, n_frames, np_, self.patch_dropout.keep_count(np_), device)
+
+    def forward_groups(self, groups, drop_path_scale=None, patch_keep=None):
         """groups: list of [B_g, C, H, W] pixel tensors (C = 3, or 1 for spectrograms evaluated with channel-summed patch
         weights - identical to repeating the channel 3x as mico.py:140 does).  Returns [sum B_g, N, D] fp32 tokens after
-        the final LayerNorm."""
+        the final LayerNorm; with patch dropout active N = 1 + keep (CLS, then the kept patches in the table's order).
+        patch_keep: int [sum B_g, keep] table of kept patch indices replacing the draw (parity tests)."""
         for g in groups:
             H, W = g.shape[-2:]
             assert H == self.patch_embed.img_size[0] and W == self.patch_embed.img_size[1], \
                 f"Input image size ({H}*{W}) doesn't match model ({self.patch_embed.img_size[0]}*{self.patch_embed.img_size[1]})."
         spec, params = self._tower_spec()
+        n_frames = sum(g.shape[0] for g in groups)
+        # the patch-dropout draw comes first: the reference draws it before any block (and its DropPath) runs
+        keep = self._patch_keep(n_frames, groups[0].device, patch_keep)
         if drop_path_scale is None:
-            drop_path_scale = self._drop_path_scale(sum(g.shape[0] for g in groups), groups[0].device)
-        return Fn.EvaTowerFn.apply(spec, tuple(groups), drop_path_scale, *params)
+            drop_path_scale = self._drop_path_scale(n_frames, groups[0].device)
+        return Fn.EvaTowerFn.apply(spec, tuple(groups), drop_path_scale, keep, *params)
 
     def forward_features(self, x, return_all_features=False):
         out = self.forward_groups([x])
@@ -192,7 +244,8 @@ class CustomCLIP(nn.Module):
             img_size=vision_cfg["image_size"], patch_size=vision_cfg["patch_size"], num_classes=embed_dim,
             embed_dim=vision_cfg["width"], depth=vision_cfg["layers"], num_heads=vision_cfg["width"] // vision_cfg["head_width"],
             mlp_ratio=vision_cfg["mlp_ratio"], drop_path_rate=vision_cfg["drop_path_rate"], rope=vision_cfg["rope"],
-            naiveswiglu=vision_cfg["naiveswiglu"], subln=vision_cfg["subln"], postnorm=vision_cfg.get("postnorm", False))
+            naiveswiglu=vision_cfg["naiveswiglu"], subln=vision_cfg["subln"], postnorm=vision_cfg.get("postnorm", False),
+            patch_dropout=vision_cfg.get("patch_dropout", 0.))
         self.text = None
         self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
 
@@ -208,9 +261,9 @@ class CustomCLIP(nn.Module):
                                   "text goes through MiCo.forward_multimodal_encoder")
 
 
-def create_model(model_name, force_custom_clip=True, image_size=None, layers=None, **_):
+def create_model(model_name, force_custom_clip=True, image_size=None, layers=None, force_patch_dropout=None, **_):
     """factory.py:211-360 for the JSON-registered EVA towers.  `layers` (not in the reference) truncates the depth for
-    tests."""
+    tests; `force_patch_dropout` sets the tower's patch-dropout rate (factory.py:264-266)."""
     if model_name not in MODEL_CONFIGS:
         raise RuntimeError(f"Model config for {model_name} not found.")
     cfg = dict(MODEL_CONFIGS[model_name])
@@ -218,4 +271,6 @@ def create_model(model_name, force_custom_clip=True, image_size=None, layers=Non
     cfg["image_size"] = image_size or 224
     if layers is not None:
         cfg["layers"] = layers
+    if force_patch_dropout is not None:
+        cfg["patch_dropout"] = force_patch_dropout
     return CustomCLIP(embed_dim, cfg)

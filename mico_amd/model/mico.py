@@ -148,6 +148,8 @@ class MMGeneralModule(nn.Module):
         name through load_state_dict like every other checkpoint here)."""
         from .swin import SWIN_CONFIGS, SwinTransformer
         t = self.config.vision_encoder_type
+        if self.config.get("patch_dropout", 0):
+            raise ValueError(f"patch_dropout = {self.config.get('patch_dropout')} is an EVA-tower option: the Swin tower ({t}) has no patch dropout")
         key = next((k for k in SWIN_CONFIGS if t.startswith(k)), None)
         if key is None:
             raise NotImplementedError(t)
@@ -161,8 +163,9 @@ class MMGeneralModule(nn.Module):
         if t not in VISION_TYPES:
             raise NotImplementedError(t)
         name, self.vision_dim = VISION_TYPES[t]
+        # patch_dropout (an addition of this repository, default 0): the tower's FLIP rate, passed as the factory's force_patch_dropout
         self.vision_encoder = create_model(name, force_custom_clip=True, image_size=self.config.vision_resolution,
-                                           layers=self.config.get("vision_layers"))
+                                           layers=self.config.get("vision_layers"), force_patch_dropout=self.config.get("patch_dropout", 0.))
 
     def construct_audio_encoder(self):
         self.audio_dim = self.vision_dim

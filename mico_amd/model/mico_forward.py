@@ -8,7 +8,8 @@ methods of mico_amd.model.mico.MiCo.
 batch keys: vision_pixels [b,n,3,h,w] | audio_spectrograms [b,n,h,w] | depth_pixels [b,n,3,h,w] (any subset);
             raw_captions (list[str]) or input_ids/attention_mask [b,S].
             optional `_injected`: {subtask: {neg_cond_idx, neg_text_idx}, "cap": {masked_ids, labels}} replaces the RNG draws
-            (torch.multinomial / TokenMasker) for parity tests; optional `_world`: simulated gathered tensors.
+            (torch.multinomial / TokenMasker) for parity tests, "drop_path_scale" / "patch_keep" ({modality: [depth, 2, b*n] /
+            int [b*n, keep]}) the tower's stochastic-depth and patch-dropout draws; optional `_world`: simulated gathered tensors.
 """
 import torch
 
@@ -53,12 +54,19 @@ def encode_batch(self, batch):
         dps = (batch.get("_injected") or {}).get("drop_path_scale")
         if dps is not None:
             dps = torch.cat([dps[m].float().cpu() for m, _, _ in meta], dim=-1)
+        # injected patch-dropout tables ({modality: int [b*n, keep]}), concatenated in the same frame order; otherwise the tower draws ONE
+        # table over all frames of the pass
+        pk = (batch.get("_injected") or {}).get("patch_keep")
+        if pk is not None:
+            pk = torch.cat([torch.as_tensor(pk[m]).cpu() for m, _, _ in meta], dim=0)
         if self.config.vision_encoder_type.startswith("swin"):
+            if pk is not None:
+                raise ValueError("patch_keep was injected but the Swin tower has no patch dropout")
             # one tower pass as well; spectrograms take the reference's route of three identical channels (mico.py:139-140)
             frames = torch.cat([g.expand(-1, 3, -1, -1) if g.shape[1] == 1 else g for g in groups], dim=0)
             tokens = self.vision_encoder.forward_features(frames, drop_path_scale=dps)
         else:
-            tokens = self.vision_encoder.visual.forward_groups(groups, drop_path_scale=dps)
+            tokens = self.vision_encoder.visual.forward_groups(groups, drop_path_scale=dps, patch_keep=pk)
         f0 = 0
         for m, b, n in meta:
             o = tokens[f0:f0 + b * n].view(b, n, *tokens.shape[-2:])

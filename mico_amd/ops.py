@@ -380,6 +380,51 @@ def im2row(pixels, rows16, P, kpad):
     check(_lib.lib().mico_im2row(_p(pixels), _p(rows16), B, Cc, H, W, P, kpad, dt_code(rows16.dtype), _st()), "mico_im2row")
 
 
+def _keep_i32(keep):
+    if keep.dtype != torch.int32 or not keep.is_contiguous() or keep.dim() != 2:
+        raise MicoHipError("patch-dropout keep tables are contiguous int32 [frames, keep] device tensors")
+    return keep
+
+
+def im2row_keep(pixels, rows16, keep, P, kpad):
+    """rows16 [B * keep, kpad] = im2row of the kept patches (keep: int32 [B, keep])."""
+    B, Cc, H, W = pixels.shape
+    keep = _keep_i32(keep)
+    assert keep.shape[0] == B and rows16.shape[0] >= B * keep.shape[1]
+    check(_lib.lib().mico_im2row_keep(_p(pixels), _p(rows16), _p(keep), B, Cc, H, W, P, kpad, keep.shape[1], dt_code(rows16.dtype), _st()),
+          "mico_im2row_keep")
+
+
+def patch_pos_keep(x, keep, cls, pos):
+    """x fp32 [B * (1 + keep), D] after the bias-only patch GEMM: CLS rows = cls + pos[0], kept rows += pos[1 + keep[f, r]]."""
+    keep = _keep_i32(keep)
+    B, nk = keep.shape
+    np_ = pos.shape[0] - 1
+    assert x.shape[0] >= B * (nk + 1) and pos.shape[1] == x.shape[1] == cls.numel() and pos.is_contiguous()
+    check(_lib.lib().mico_patch_pos_keep(_p(x), x.stride(0), _p(keep), B, nk, _p(cls), _p(pos), np_, x.shape[1], _st()), "mico_patch_pos_keep")
+
+
+def rope_keep(x, bs, rs, B, N, H, hd, cos_t, sin_t, keep, frame_map=None, inverse=False):
+    """ops.rope with per-frame table rows: token 1 + n of frame b uses row keep[frame_map[b] if frame_map is not None else b, n]."""
+    keep = _keep_i32(keep)
+    assert keep.shape[1] == N - 1
+    check(_lib.lib().mico_rope_keep(_p(x), bs, rs, B, N, H, hd, _p(cos_t), _p(sin_t), _p(keep), keep.shape[0], _p(frame_map),
+                                    cos_t.shape[0], int(inverse), dt_code(x.dtype), _st()), "mico_rope_keep")
+
+
+def pos_grad_keep(g, keep, np_, dpos=None, inv_ws=None):
+    """Positional-table gradient of a dropped pass: g fp32 [B * (1 + keep), D] -> dpos fp32 [1 + np_, D] (deterministic, no atomics)."""
+    keep = _keep_i32(keep)
+    B, nk = keep.shape
+    D = g.shape[1]
+    assert g.shape[0] >= B * (nk + 1)
+    dpos = dpos if dpos is not None else torch.empty((np_ + 1, D), dtype=torch.float32, device=g.device)
+    inv_ws = inv_ws if inv_ws is not None else torch.empty(max(1, B * np_), dtype=torch.int32, device=g.device)
+    assert dpos.is_contiguous() and dpos.numel() >= (np_ + 1) * D and inv_ws.numel() >= B * np_
+    check(_lib.lib().mico_pos_grad_keep(_p(g), g.stride(0), _p(keep), B, nk, np_, D, _p(inv_ws), _p(dpos), _st()), "mico_pos_grad_keep")
+    return dpos
+
+
 def cast_f32_to_16(src, dst, *, cols=None, cols_pad=None, scale=1.0):
     rows = src.shape[0]
     cols = cols if cols is not None else src.shape[1]

@@ -307,6 +307,30 @@ int mico_attn_bwd(const void* q, const void* k, const void* v, const void* o, co
                   void* dq, void* dk, void* dv, float* delta,
                   const mico_attn_params* p, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Incremental decoding (csrc/decode.hip; functional.BertDecodeCache).  Inference only, 16-bit operands, hd 64 only.
+ *
+ * Grouped-query decode attention: `sets` key sets, each read by rows_per_set x q_per_row queries.  Query (s, r, i) of head h
+ * is q[((s rows_per_set + r) q_per_row + i) q_rs + h hd .. + hd), its output the same place in o (o_rs); key n of set s is
+ * k[s kv_ss + n kv_rs + h hd ..], its value v[s kv_ss + n kv_rs + h hd ..] (n < Sk).  scores = (q . k) scale + mask[(s rows_per_set
+ * + r) mask_rs + i mask_qs + n] (fp32 additive, the extended_attention_mask semantics (1 - m) -10000; NULL: none), softmax and
+ * accumulation fp32.  splits > 1 splits the keys of every (set, head) over up to `splits` workgroups (in whole 64-key blocks);
+ * their partial (max, sum, o) are folded in split order by a second launch (bit-identical from run to run, no atomics) and need the
+ * fp32 workspace ws of mico_attn_decode_ws_bytes(sets, H, rows_per_set * q_per_row, Sk, splits) bytes (0: none needed; -1: bad
+ * arguments).  q / k / v / o 16-byte aligned, strides multiples of 8 elements. */
+int mico_attn_decode_ws_bytes(int sets, int H, int QR, int Sk, int splits);
+int mico_attn_decode(const void* q, int64_t q_rs, const void* k, const void* v, int64_t kv_ss, int64_t kv_rs, void* o, int64_t o_rs,
+                     const float* mask, int64_t mask_rs, int64_t mask_qs, int sets, int rows_per_set, int q_per_row, int H, int Sk,
+                     int hd, float scale, int splits, float* ws, int64_t ws_bytes, int dtype, void* stream);
+/* K/V-cache upkeep (16-bit elements, 16-byte aligned, widths / strides multiples of 8):
+ * append:  cache[r cache_ss + (pos0 + i) cache_rs + c] = src[(r n_new + i) src_rs + c]   (r < rows, i < n_new, c < width);
+ * gather:  dst[l layer_stride + r row_stride + e] = src[l layer_stride + parent[r] row_stride + e]   (l < layers, r < rows, e < n;
+ *          parent: int64 device array, entries outside [0, rows) leave their row unwritten; src != dst). */
+int mico_decode_kv_append(const void* src, int64_t src_rs, void* cache, int64_t cache_ss, int64_t cache_rs, int rows, int n_new,
+                          int pos0, int width, void* stream);
+int mico_decode_kv_gather(const void* src, void* dst, const int64_t* parent, int layers, int rows, int64_t layer_stride,
+                          int64_t row_stride, int64_t n, void* stream);
+
 /* RoPE on tokens 1.. of a [B, N, H, hd] (row stride rs, batch stride bs) buffer, in place; inverse = transposed
  * rotation for the backward.  cos/sin fp32 [N-1, hd].  rope.py:121-137, eva_vit_model.py:314-322. */
 int mico_rope(void* x, int64_t bs, int64_t rs, int B, int N, int H, int hd, const float* cos_t, const float* sin_t,

@@ -99,8 +99,9 @@ def write_synthetic_pretrain_dir(path, vision_encoder_type="evaclip01_giant", st
 
 
 @torch.no_grad()
-def run_demo(model, image_input, texts, device="cuda", max_length=30):
-    """The retrieval + matching part of the reference's __main__ (inference_demo.py:128-158)."""
+def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False):
+    """The retrieval + matching part of the reference's __main__ (inference_demo.py:128-158).  use_cache: the caption's beam search
+    decodes incrementally (BertForMaskedLM.generate(use_cache=True))."""
     image_input = image_input.to(device).unsqueeze(1)          # image as a 1 frame video
     video_output = model.forward_vision_encoder(image_input)
     feat_v = F.normalize(model.contra_head_v(model.pool_vision_for_contra(video_output)), dim=-1)
@@ -120,7 +121,7 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30):
     outputs = model.multimodal_encoder.generate(input_ids=init_ids, attention_mask=init_ids.new_ones(cap_input.size(0), 1, 1),
                                                 encoder_hidden_states=cap_input, max_new_tokens=model.max_caption_len,
                                                 num_beams=model.beam_size, eos_token_id=tk.sep_token_id,
-                                                pad_token_id=tk.pad_token_id, length_penalty=0.6)
+                                                pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=use_cache)
     captions = tk.batch_decode(outputs[:, 1:], skip_special_tokens=True)
     return dict(feat_v=feat_v, feat_t=feat_t, sim_t2v=sim_t2v, itm_scores=slice_scores, input_ids=input_ids,
                 caption_ids=outputs, captions=captions)
@@ -133,6 +134,7 @@ def main():
     ap.add_argument("--image", default="example/test.jpeg")
     ap.add_argument("--texts", nargs="*", default=["a man is skiing in a snowy day.", "it's a hot day"])
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
+    ap.add_argument("--use_cache", action="store_true", help="decode the caption incrementally (K/V cache; same caption)")
     args = ap.parse_args()
     device = "cuda"
     from mico_amd import runtime
@@ -148,7 +150,7 @@ def main():
     image_input = proc(args.image)
     if image_input is None:
         raise SystemExit(f"cannot read {args.image}")
-    out = run_demo(model, image_input, args.texts, device)
+    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache)
     print(out["sim_t2v"])
     print(out["itm_scores"])
     print(out["captions"])

@@ -77,6 +77,11 @@ PROTOTYPES = {
     "mico_layernorm_bwd": [C.POINTER(LnBwdParams), c_int, c_vp],
     "mico_attn_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, C.POINTER(AttnParams), c_int, c_vp],
     "mico_attn_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.POINTER(AttnParams), c_int, c_vp],
+    "mico_attn_decode_ws_bytes": [c_int, c_int, c_int, c_int, c_int],
+    "mico_attn_decode": [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
+                         c_int, c_f, c_int, c_vp, c_i64, c_int, c_vp],
+    "mico_decode_kv_append": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp],
+    "mico_decode_kv_gather": [c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp],
     "mico_rope": [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
     "mico_im2row": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "mico_im2row_keep": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
@@ -137,7 +142,7 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 115   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 116   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):

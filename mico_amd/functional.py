@@ -2179,6 +2179,147 @@ class LMLogitsFn(torch.autograd.Function):
         raise RuntimeError("LMLogitsFn is inference-only; use labels=... to train the captioning head")
 
 
+class BertDecodeCache:
+    """Incremental decoding of BertForMaskedLM.generate (use_cache=True) under the reference's [MASK]-append protocol (bert.py:1110-1143).
+    Inference only, no autograd.  Under that protocol no position attends to a later one, so every layer's hidden state of position p
+    depends on tokens <= p only, and from one step to the next exactly two positions change: t - 1 (the [MASK] that became the chosen
+    token) and t (the new [MASK]).  The cache keeps:
+      kv      per-layer self-attention K / V of every row, [L, rows, max_len, 2 D] (a second buffer for the beam re-gather);
+      kvx     cross-attention K / V of the condition tokens, projected ONCE PER CONDITION SET: [sets E, L * 2 D] (CrossKVFn's interleaved
+              layout), read by the rows_per_set rows of a set (beams, or sampled captions) through mico_attn_decode;
+      mask    the additive mask (extended_attention_mask) of the fully grown 3-D mask, [rows, max_len, max_len] fp32.
+    The first pass (prefill) runs the prompt plus [MASK] (all prompt positions), every later pass 2 rows per sequence; only the [MASK]
+    row goes through the LM head.  Precision: runtime.compute_dtype() / split_activations() as BertFn."""
+
+    passes = None      # tests: a list, when set, receives (rows, positions per row) of every pass
+
+    def __init__(self, spec, params, head, cond, rows_per_set, mask, mask_token_id):
+        """params: BertModel's parameters in spec order; head: the LM head's (transform W, b, LN gamma, beta, decoder W, b);
+        cond: fp32 [sets, E, D] condition tokens or None; mask: {0, 1} [rows, max_len, max_len], the prompt's 3-D mask grown to the
+        longest sequence the decode reaches (rows = sets * rows_per_set, sample-major)."""
+        if any(p.requires_grad for p in params) and torch.is_grad_enabled():
+            raise RuntimeError("BertDecodeCache is an inference feature: call under torch.no_grad()")
+        # (the parameter objects themselves, not detached views: runtime's 16-bit weight cache is keyed on the object - a fresh view per
+        # pass would re-cast every weight at every step)
+        self.spec, self.head, self.mask_token_id = spec, list(head), int(mask_token_id)
+        P = lambda n: params[spec.idx[n]]
+        self.P = P
+        dev = mask.device
+        D, L = spec.D, spec.L
+        self.dt = dt = runtime.compute_dtype()
+        self.rows, self.max_len = mask.shape[0], mask.shape[1]
+        self.R = int(rows_per_set)
+        if self.rows % self.R:
+            raise ValueError(f"BertDecodeCache: {self.rows} rows are not a whole number of sets of {self.R}")
+        self.sets = self.rows // self.R
+        if self.max_len > P("embeddings.position_embeddings.weight").shape[0]:
+            raise ValueError(f"BertDecodeCache: {self.max_len} positions exceed the position table")
+        self.mask = ((1.0 - mask.to(torch.float32)) * -10000.0).contiguous()
+        self.kv = _empty((L, self.rows, self.max_len, 2 * D), dt, dev)
+        self.alt = None
+        self.filled = 0
+        self.bqkv = [torch.cat([P(f"encoder.layer.{li}.attention.self.{n}.bias") for n in ("query", "key", "value")]) for li in range(L)]
+        self.kvx, self.E = None, 0
+        if cond is not None:
+            if cond.shape[0] != self.sets:
+                raise ValueError(f"BertDecodeCache: {cond.shape[0]} condition sets for {self.rows} rows of {self.R} per set")
+            self.E = E = cond.shape[1]
+            cond16 = _empty((self.sets * E, D), dt, dev)
+            ops.cast_f32_to_16(cond.float().contiguous().view(self.sets * E, D), cond16)
+            kvp = []
+            for li in range(L):
+                ca = f"encoder.layer.{li}.crossattention.self."
+                kvp += [params[spec.idx[ca + n]] for n in ("key.weight", "key.bias", "value.weight", "value.bias")]
+            self.kvx = _empty((self.sets * E, L * 2 * D), dt, dev)
+            _fwd_gemm(cond16, "bkv_all", _kv_all_weights(kvp, L), self.kvx,
+                      bias=torch.cat([kvp[4 * li + j].detach() for li in range(L) for j in (1, 3)]))
+
+    def reorder(self, parent):
+        """Beam search: row r continues the prefix of row parent[r] (int64 [rows]) - the cached positions that stay, [0, filled - 1),
+        are re-gathered (the last one, the old [MASK], is rewritten by the next pass)."""
+        if self.alt is None:
+            self.alt = torch.empty_like(self.kv)
+        ops.decode_kv_gather(self.kv, self.alt, parent.to(self.kv.device), self.filled - 1)
+        self.kv, self.alt = self.alt, self.kv
+
+    def next_token_logits(self, ids, parent=None):
+        """= BertForMaskedLM.next_token_logits(ids, mask, cond) of the recomputing path: fp32 logits [rows, vocab] of the [MASK] appended
+        to ids.  The first call runs the prompt; every later one expects ids grown by one token (after reorder by `parent`, int64 [rows]
+        host tensor or None, when rows were re-ordered) and runs positions t - 1, t only."""
+        rows, cur = ids.shape
+        dummy = torch.full((rows, 1), self.mask_token_id, dtype=torch.long, device=ids.device)
+        if self.filled == 0:
+            return self.run(torch.cat([ids, dummy], 1), 0)
+        if cur != self.filled:
+            raise ValueError(f"BertDecodeCache: ids of length {cur} after a pass over {self.filled} positions (one token per step)")
+        if parent is not None and not torch.equal(parent.cpu(), torch.arange(rows)):
+            self.reorder(parent)
+        return self.run(torch.cat([ids[:, -1:], dummy], 1), cur - 1)
+
+    def run(self, ids, pos0):
+        """One pass over positions pos0 .. pos0 + n - 1 of every row (ids [rows, n]): appends their K / V to the cache, returns the fp32
+        LM logits of the last position [rows, vocab]."""
+        spec, P, dt = self.spec, self.P, self.dt
+        rows, n = ids.shape
+        if rows != self.rows or pos0 + n > self.max_len:
+            raise ValueError(f"BertDecodeCache: a pass over {rows} rows at positions {pos0} .. {pos0 + n - 1} (cache: {self.rows} rows, "
+                             f"{self.max_len} positions)")
+        if BertDecodeCache.passes is not None:
+            BertDecodeCache.passes.append((rows, n))
+        dev = ids.device
+        D, H, I, L = spec.D, spec.H, spec.I, spec.L
+        hd = D // H
+        N = rows * n
+        scale = 1.0 / math.sqrt(hd)
+        emb = _empty((N, D), torch.float32, dev)
+        # positions pos0 .. pos0 + n - 1: the table from row pos0 on (mico_bert_embed_fwd gives row r position r mod n)
+        ops.bert_embed_fwd(ids.contiguous(), P("embeddings.word_embeddings.weight"), P("embeddings.position_embeddings.weight")[pos0:],
+                           P("embeddings.token_type_embeddings.weight")[0].contiguous(), emb, n)
+        split = runtime.split_activations()
+
+        def ln_out(u, pre):
+            o32, o16 = _empty((N, D), torch.float32, dev), _empty((N, 2 * D if split else D), dt, dev)
+            ops.layernorm_fwd(u, P(pre + "LayerNorm.weight"), P(pre + "LayerNorm.bias"), spec.eps, out16=o16, out32=o32, split16=split, dtype=dt)
+            return o32, o16
+
+        x32, x16 = ln_out(emb, "embeddings.")
+        sk = pos0 + n
+        for li in range(L):
+            p = f"encoder.layer.{li}."
+            sa = p + "attention.self."
+            qkv = _empty((N, 3 * D), dt, dev)
+            _fwd_gemm(x16, "bqkv", [P(sa + "query.weight"), P(sa + "key.weight"), P(sa + "value.weight")], qkv, bias=self.bqkv[li])
+            kv = self.kv[li]
+            ops.decode_kv_append(qkv[:, D:], kv, rows=rows, n_new=n, pos0=pos0)
+            co = _empty((N, D), dt, dev)
+            # self-attention: every row is a key set of its own (its cache), read by its n new positions under their mask rows
+            ops.attn_decode(qkv, kv, kv[:, :, D:], co, sets=rows, rows_per_set=1, q_per_row=n, H=H, Sk=sk, hd=hd, scale=scale, q_rs=3 * D,
+                            kv_strides=(kv.stride(0), kv.stride(1)), o_rs=D, mask=self.mask[:, pos0:],
+                            mask_strides=(self.mask.stride(0), self.mask.stride(1)))
+            u = _empty((N, D), torch.float32, dev)
+            _fwd_gemm(co, "w1", [P(p + "attention.output.dense.weight")], u, bias=P(p + "attention.output.dense.bias"), resid=x32)
+            x32, x16 = ln_out(u, p + "attention.output.")
+            if self.kvx is not None:
+                ca = p + "crossattention.self."
+                q = _empty((N, D), dt, dev)
+                _fwd_gemm(x16, "w1", [P(ca + "query.weight")], q, bias=P(ca + "query.bias"))
+                cc = _empty((N, D), dt, dev)
+                kvl = self.kvx[:, li * 2 * D:]
+                # cross-attention: the rows_per_set x n queries of a condition set share its keys
+                ops.attn_decode(q, kvl, kvl[:, D:], cc, sets=self.sets, rows_per_set=self.R, q_per_row=n, H=H, Sk=self.E, hd=hd, scale=scale,
+                                q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
+                u2 = _empty((N, D), torch.float32, dev)
+                _fwd_gemm(cc, "w1", [P(p + "crossattention.output.dense.weight")], u2, bias=P(p + "crossattention.output.dense.bias"), resid=x32)
+                x32, x16 = ln_out(u2, p + "crossattention.output.")
+            act = _empty((N, I), dt, dev)
+            _fwd_gemm(x16, "w1", [P(p + "intermediate.dense.weight")], act, bias=P(p + "intermediate.dense.bias"), act=ops.ACT_GELU)
+            u3 = _empty((N, D), torch.float32, dev)
+            _fwd_gemm(act, "w1", [P(p + "output.dense.weight")], u3, bias=P(p + "output.dense.bias"), resid=x32)
+            x32, x16 = ln_out(u3, p + "output.")
+        self.filled = sk
+        return LMLogitsFn.apply(x32.view(rows, n, D)[:, n - 1:, :], *self.head)[:, 0, :]
+
+
 # ======================================================================================================================
 # cross entropy over small fp32 logits (ITC with label smoothing, ITM)  - vast.py:411-415, 455
 # ======================================================================================================================

@@ -266,28 +266,52 @@ class BertForMaskedLM(nn.Module):
         last = seq[:, -1:, :].contiguous()
         return Fn.LMLogitsFn.apply(last, *[p.detach() for p in self._head_params()])[:, 0, :]
 
+    def _decode_cache(self, input_ids, attention_mask, cond, rows_per_set, max_length):
+        """functional.BertDecodeCache for a decode of input_ids / attention_mask ([rows, n], [rows, n, n]) that reaches max_length
+        positions; cond [rows / rows_per_set, E, D] (one condition set per rows_per_set consecutive rows) or None."""
+        mask = attention_mask
+        while mask.shape[1] < max_length:
+            mask = self.update_attention_mask(mask)
+        spec, params = self.bert._bert_spec()
+        return Fn.BertDecodeCache(spec, params, self._head_params(), cond, rows_per_set, mask, self.tokenizer.mask_token_id)
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, max_new_tokens=20, num_beams=1,
-                 eos_token_id=None, pad_token_id=None, length_penalty=1.0, do_sample=False, top_k=50, sample_noise=None, **unused):
+                 eos_token_id=None, pad_token_id=None, length_penalty=1.0, do_sample=False, top_k=50, sample_noise=None,
+                 use_cache=False, num_return_sequences=1, **unused):
         """Beam search with the semantics of transformers==4.31 GenerationMixin.generate / BeamSearchScorer as the reference
         calls it (inference_demo.py:164-171: num_beams 3, length_penalty 0.6, early_stopping False, no logits processors):
         2*num_beams candidates per step, finished hypotheses scored sum_logprob / len**length_penalty, the "cannot improve"
         stop heuristic, finalisation with the open beams, eos-terminated pad-filled output.  The search bookkeeping runs on
-        the host over 2*num_beams candidates per sample; the model step and log-softmax / top-k run on the device."""
+        the host over 2*num_beams candidates per sample; the model step and log-softmax / top-k run on the device.
+        use_cache: incremental decoding (functional.BertDecodeCache) - one pass over the prompt, then 2 positions per row and step;
+        the rows of one condition set (beams, sampled captions) share its cross-attention K/V.  Same ids as the recomputing path up to
+        floating-point reduction order.  num_return_sequences (sampling only): n rows per condition set, sample-major."""
         if unused:
             raise TypeError(f"generate(): unsupported arguments {sorted(unused)}")
+        nrs = int(num_return_sequences)
+        if nrs < 1 or (nrs != 1 and not do_sample):
+            raise ValueError("generate(): num_return_sequences > 1 is provided for sampling (do_sample=True) only")
+        if use_cache and self.training:
+            raise RuntimeError("generate(use_cache=True) is inference-only (the cached decode has no BERT dropout): call .eval() first")
         if do_sample:
             if int(num_beams) != 1:
                 raise TypeError("generate(): do_sample with num_beams > 1 (beam sampling) is not used by the reference and not provided")
-            return self._sample(input_ids, attention_mask, encoder_hidden_states, max_new_tokens, int(top_k), eos_token_id,
-                                pad_token_id, sample_noise)
+            enc = encoder_hidden_states
+            if nrs > 1:      # sample-major rows b * n + i (vast.py:519-536 expands the condition the same way)
+                input_ids, attention_mask = input_ids.repeat_interleave(nrs, dim=0), attention_mask.repeat_interleave(nrs, dim=0)
+                if enc is not None and not use_cache:
+                    enc = enc.repeat_interleave(nrs, dim=0)
+            return self._sample(input_ids, attention_mask, enc, max_new_tokens, int(top_k), eos_token_id,
+                                pad_token_id, sample_noise, nrs if use_cache else 0)
         dev = input_ids.device
         B, cur = input_ids.shape
         nb = int(num_beams)
         max_length = cur + int(max_new_tokens)
         ids = input_ids.repeat_interleave(nb, dim=0)
         mask = attention_mask.repeat_interleave(nb, dim=0)
-        enc = encoder_hidden_states.repeat_interleave(nb, dim=0).contiguous() if encoder_hidden_states is not None else None
+        dec = self._decode_cache(ids, mask, encoder_hidden_states, nb, max_length) if use_cache else None
+        enc = encoder_hidden_states.repeat_interleave(nb, dim=0).contiguous() if encoder_hidden_states is not None and dec is None else None
         beam_scores = torch.zeros(B, nb, dtype=torch.float32, device=dev)
         beam_scores[:, 1:] = -1e9
         beam_scores = beam_scores.view(-1)
@@ -296,8 +320,12 @@ class BertForMaskedLM(nn.Module):
         # every beam of a sample attends to the same condition tokens and beams are only ever reordered within their sample, so
         # the per-layer cross-attention K/V of `enc` are step-invariant: projected at the first step, reused afterwards
         kv_cache = {} if enc is not None else None
+        parent = None
         while True:
-            logits = self.next_token_logits(ids, mask, enc, kv_cache).float()
+            if dec is not None:
+                logits = dec.next_token_logits(ids, parent).float()
+            else:
+                logits = self.next_token_logits(ids, mask, enc, kv_cache).float()
             scores = torch.log_softmax(logits, dim=-1) + beam_scores[:, None]
             V = scores.shape[-1]
             top_s, top_i = torch.topk(scores.view(B, nb * V), 2 * nb, dim=1, largest=True, sorted=True)
@@ -326,8 +354,10 @@ class BertForMaskedLM(nn.Module):
                         break
                 done[b] = done[b] or hyps[b].is_done(float(top_s[b].max()), cur_len)
             beam_scores = nxt_s.view(-1).to(dev)
-            ids = torch.cat([ids[nxt_b.view(-1).to(dev)], nxt_t.view(-1, 1).to(dev)], dim=1)
-            mask = self.update_attention_mask(mask)
+            parent = nxt_b.view(-1)
+            ids = torch.cat([ids[parent.to(dev)], nxt_t.view(-1, 1).to(dev)], dim=1)
+            if dec is None:
+                mask = self.update_attention_mask(mask)
             if all(done) or ids.shape[1] >= max_length:
                 break
         ids_cpu, fin = ids.cpu(), beam_scores.cpu()
@@ -347,24 +377,29 @@ class BertForMaskedLM(nn.Module):
         return out.to(dev)
 
 
-    def _sample(self, input_ids, attention_mask, enc, max_new_tokens, top_k, eos_token_id, pad_token_id, noise):
+    def _sample(self, input_ids, attention_mask, enc, max_new_tokens, top_k, eos_token_id, pad_token_id, noise, cache_rows_per_set=0):
         """Top-k sampling as the reference's captioner_mode asks transformers 4.31 for it (vast.py:526-536: do_sample=True, top_k=10,
         temperature 1): per step the top_k logits are kept (TopKLogitsWarper), softmax over them, ONE draw per row; rows that have
         produced eos emit pad from then on; stop when every row has finished or max_length is reached.  The draw is inverse-CDF over
         the kept candidates in descending-score order with one uniform number per (row, step): `noise` [rows, max_new_tokens] injects
         them (parity tests), otherwise they come from torch's generator - the same distribution as torch.multinomial, not the same
-        stream.  Device: model step + top-k; host: k candidates per row."""
+        stream.  Device: model step + top-k; host: k candidates per row.
+        cache_rows_per_set > 0: the cached decode (BertDecodeCache) with `enc` holding one condition set per cache_rows_per_set rows."""
         dev = input_ids.device
         B, cur = input_ids.shape
         max_length = cur + int(max_new_tokens)
         ids, mask = input_ids, attention_mask
         unfinished = torch.ones(B, dtype=torch.bool)
-        kv_cache = {} if enc is not None else None
+        dec = self._decode_cache(ids, mask, enc, cache_rows_per_set, max_length) if cache_rows_per_set else None
+        kv_cache = {} if enc is not None and dec is None else None
         if enc is not None:
             enc = enc.contiguous()
         step = 0
         while True:
-            logits = self.next_token_logits(ids, mask, enc, kv_cache).float()
+            if dec is not None:
+                logits = dec.next_token_logits(ids).float()
+            else:
+                logits = self.next_token_logits(ids, mask, enc, kv_cache).float()
             top_s, top_i = torch.topk(logits, min(top_k, logits.shape[-1]), dim=-1, largest=True, sorted=True)
             probs = torch.softmax(top_s, dim=-1).cpu().double()
             top_i = top_i.cpu()
@@ -376,7 +411,8 @@ class BertForMaskedLM(nn.Module):
                 tok = torch.where(unfinished, tok, torch.full_like(tok, pad_token_id if pad_token_id is not None else 0))
                 unfinished = unfinished & (tok != eos_token_id)
             ids = torch.cat([ids, tok.view(-1, 1).to(dev)], dim=1)
-            mask = self.update_attention_mask(mask)
+            if dec is None:
+                mask = self.update_attention_mask(mask)
             step += 1
             if not bool(unfinished.any()) or ids.shape[1] >= max_length:
                 break

@@ -353,25 +353,33 @@ def forward(self, batch, task, compute_loss=True, backward_scale=None):
                 runtime.mem_trace("after forward_cap")
             else:   # evaluation dict of vast.py:513-547: beam-search captions per sub-task (captioner_mode sampling is not provided)
                 tk = self.multimodal_encoder.tokenizer
+                # decode_use_cache: incremental decoding (BertForMaskedLM.generate(use_cache=True)); the rows of a sample share its
+                # condition tokens' cross-attention K/V instead of a copy each
+                cached = bool(self.config.get("decode_use_cache", False))
                 for st in subtasks:
                     cond = _condition_feats(self, enc, st[1:])
                     if self.config.get("captioner_mode", False):
                         # vast.py:519-536: generate_nums sampled captions per sample (top-k 10 sampling), rows sample-major
                         gn = int(self.config.generate_nums)
-                        cond = cond.unsqueeze(1).expand(-1, gn, -1, -1).reshape(-1, *cond.shape[1:]).contiguous()
+                        nrs = 1
+                        if cached:
+                            nrs = gn
+                        else:
+                            cond = cond.unsqueeze(1).expand(-1, gn, -1, -1).reshape(-1, *cond.shape[1:]).contiguous()
                         init = torch.full((cond.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=cond.device)
                         ids = self.multimodal_encoder.generate(input_ids=init, attention_mask=init.new_ones(cond.shape[0], 1, 1),
                                                                do_sample=True, top_k=10, encoder_hidden_states=cond,
                                                                max_new_tokens=self.max_caption_len, eos_token_id=tk.sep_token_id,
                                                                pad_token_id=tk.pad_token_id,
-                                                               sample_noise=(batch.get("_injected") or {}).get("sample_noise"))
+                                                               sample_noise=(batch.get("_injected") or {}).get("sample_noise"),
+                                                               use_cache=cached, num_return_sequences=nrs)
                         out[f"generated_captions_{st}"] = tk.batch_decode(ids[:, 1:], skip_special_tokens=True)
                         continue
                     init = torch.full((cond.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=cond.device)
                     ids = self.multimodal_encoder.generate(input_ids=init, attention_mask=init.new_ones(cond.shape[0], 1, 1),
                                                            encoder_hidden_states=cond, max_new_tokens=self.max_caption_len,
                                                            num_beams=self.beam_size, eos_token_id=tk.sep_token_id,
-                                                           pad_token_id=tk.pad_token_id, length_penalty=0.6)
+                                                           pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=cached)
                     out[f"generated_captions_{st}"] = tk.batch_decode(ids[:, 1:], skip_special_tokens=True)
         else:
             raise NotImplementedError(t)

@@ -360,6 +360,55 @@ def attn_fwd(q, k, v, o, lse, *, B, H, Sq, Sk, hd, scale, mask=None, q_strides, 
     check(rc, "mico_attn_fwd")
 
 
+DECODE_TARGET_WGS = 2048   # one-wave workgroups of mico_attn_decode the key split aims for (256 CUs x 8 waves in flight)
+DECODE_QCHUNK = 4          # queries per workgroup (DEC_QC in csrc/decode.hip)
+
+
+def attn_decode_splits(sets, H, QR, Sk):
+    """Key split of mico_attn_decode: enough workgroups to fill the chip when sets x heads cannot (a whole 64-key block at least per split)."""
+    items = sets * H * (-(-QR // DECODE_QCHUNK))
+    return max(1, min(-(-Sk // 64), -(-DECODE_TARGET_WGS // items)))
+
+
+def attn_decode(q, k, v, o, *, sets, rows_per_set, q_per_row, H, Sk, hd, scale, q_rs, kv_strides, o_rs, mask=None, mask_strides=(0, 0),
+                splits=None):
+    """Grouped-query decode attention (mico_attn_decode): `sets` key sets of Sk keys, each read by rows_per_set x q_per_row queries.
+    q / o: 16-bit, query (s, r, i) at row (s rows_per_set + r) q_per_row + i (row strides q_rs / o_rs, head h at columns h hd ..);
+    k / v: key n of set s at s kv_strides[0] + n kv_strides[1]; mask: fp32 additive, row of query (s, r, i) at
+    (s rows_per_set + r) mask_strides[0] + i mask_strides[1].  splits: key split (None: attn_decode_splits)."""
+    if hd != 64:
+        raise MicoHipError(f"attn_decode: head size {hd} is not supported (hd 64 only)")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype or o.dtype != q.dtype:
+        raise MicoHipError("attn_decode: q / k / v / o must share one 16-bit dtype")
+    if mask is not None and mask.dtype != torch.float32:
+        raise MicoHipError("attn_decode: the mask is fp32 additive")
+    QR = rows_per_set * q_per_row
+    splits = attn_decode_splits(sets, H, QR, Sk) if splits is None else int(splits)
+    l = _lib.lib()
+    nbytes = l.mico_attn_decode_ws_bytes(sets, H, QR, Sk, splits)
+    if nbytes < 0:
+        raise MicoHipError(f"attn_decode: bad shape (sets {sets}, H {H}, queries {QR}, Sk {Sk}, splits {splits})")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    check(l.mico_attn_decode(_p(q), q_rs, _p(k), _p(v), kv_strides[0], kv_strides[1], _p(o), o_rs, _p(mask), mask_strides[0], mask_strides[1],
+                             sets, rows_per_set, q_per_row, H, Sk, hd, scale, splits, _p(ws), nbytes, dt_code(q.dtype), _st()),
+          "mico_attn_decode")
+
+
+def decode_kv_append(src, cache, *, rows, n_new, pos0):
+    """cache [rows, max_len, width] (row stride per position) <- src rows r n_new + i at positions pos0 + i (16-bit, src [rows n_new, >= width])."""
+    width = cache.shape[-1]
+    check(_lib.lib().mico_decode_kv_append(_p(src), src.stride(0), _p(cache), cache.stride(0), cache.stride(1), rows, n_new, pos0, width, _st()),
+          "mico_decode_kv_append")
+
+
+def decode_kv_gather(src, dst, parent, n):
+    """dst[l, r, :n positions] = src[l, parent[r], :n positions] for caches [layers, rows, max_len, width]; parent int64 [rows] on the device."""
+    Lr, rows = src.shape[0], src.shape[1]
+    assert src.shape == dst.shape and src.is_contiguous() and dst.is_contiguous() and parent.dtype == torch.int64 and parent.numel() == rows
+    check(_lib.lib().mico_decode_kv_gather(_p(src), _p(dst), _p(parent.contiguous()), Lr, rows, src.stride(0), src.stride(1),
+                                           n * src.stride(2), _st()), "mico_decode_kv_gather")
+
+
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, delta, *, B, H, Sq, Sk, hd, scale, mask=None, q_strides, k_strides,
              v_strides, o_strides, drop=None, kv_batch_mod=0, batch0=0, dkv_accumulate=False):
     """kv_batch_mod > 0: k / v hold kv_batch_mod batch entries shared modulo (see mico_attn_params); dk / dv are [B, ...] as always.

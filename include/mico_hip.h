@@ -297,6 +297,14 @@ typedef struct mico_attn_params {
      * read-modify-write) instead of overwriting it - the second launch over the ITM triplet's third third, whose K/V set is the first
      * third's, leaves the sum in place (no per-entry dK/dV buffer, no add pass). */
     int dkv_accumulate;
+    /* Indexed K/V (ABI 117; mico_attn_fwd only, inference): device pointer to B int32 values - batch entry b reads K/V set kv_index[b]
+     * (k + kv_index[b] * k_bs, v + kv_index[b] * v_bs), so B is independent of the number of sets: the (text, candidate) pairs of a retrieval
+     * re-ranking read a K/V memory that holds every candidate once.  The mask, q, o and lse stay per batch entry.  Every value must lie in
+     * [0, sets): the CALLER guarantees it - the kernel reads the table as it is and the library cannot see how many sets the buffers hold
+     * (mico_amd.evaluation builds the table on the host, so no device sync is needed to check it).  Not combinable with kv_batch_mod
+     * (MICO_EINVAL); mico_attn_bwd refuses it (MICO_EINVAL): dK / dV would need a scatter-add over the readers of a set.  Launches with a
+     * table always take the tiled kernel (never the K/V-resident one).  NULL: every batch entry has its own K/V (or kv_batch_mod). */
+    const int* kv_index;
 } mico_attn_params;
 
 int mico_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
@@ -446,6 +454,12 @@ int mico_embed_scatter_add(const int64_t* ids, const float* dsum, float* dword, 
  * caller (injected for parity, torch.rand otherwise); out[r] = #{j : cdf_r[j] <= u[r] * total_r} (inverse-CDF draw: the first column whose CDF
  * exceeds the target, so a zero-weight column is never drawn), int64. */
 int mico_itm_sample(const float* sim, int64_t ld, int rows, int cols, int diag_offset, const float* u, int64_t* out, void* stream);
+/* Row-wise top-k of an fp32 [rows, cols] matrix (row stride row_stride elements) - the ITC shortlist of retrieval evaluation (the candidates
+ * that compute_slice_scores, vast.py:373-380, re-ranks; itm_rerank_num, data/utils/args.py:259); replaces torch.topk and its sort workspaces.
+ * idx_out int32 [rows, k], val_out fp32 [rows, k] (val_out may be NULL): the k largest entries of every row in descending order, equal values
+ * in ascending column order (the order is total, so the result is reproducible).  NaN entries rank below every number.  1 <= k <= 128,
+ * k <= cols.  One pass over the matrix: every element is read from HBM once, one wave per row. */
+int mico_topk_rows(const float* sim, int64_t row_stride, int rows, int cols, int k, int* idx_out, float* val_out, void* stream);
 /* Caption-loss token masking (TokenMasker.perform_mask, data/model/general_module.py:64-97 - there two Python loops over b x S on the host behind
  * a .cpu() copy, i.e. a stream sync per step).  tokens: int64 [rows, S].  A token at position j >= 1 with id != 0 is selected when
  * u_mask[r][row][j] < mask_prob; round r = 0 stands unless it selects nothing in the row, then round 1 is drawn, ... (the reference's

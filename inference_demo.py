@@ -99,9 +99,11 @@ def write_synthetic_pretrain_dir(path, vision_encoder_type="evaclip01_giant", st
 
 
 @torch.no_grad()
-def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False):
+def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False, rerank=False):
     """The retrieval + matching part of the reference's __main__ (inference_demo.py:128-158).  use_cache: the caption's beam search
-    decodes incrementally (BertForMaskedLM.generate(use_cache=True))."""
+    decodes incrementally (BertForMaskedLM.generate(use_cache=True)).  rerank: the ITM scores come from the retrieval evaluation path
+    (mico_amd.evaluation.rerank_retrieval: the image's condition tokens projected once, every text reading them by index) instead of one
+    copy of the tokens per text - the same scores."""
     image_input = image_input.to(device).unsqueeze(1)          # image as a 1 frame video
     video_output = model.forward_vision_encoder(image_input)
     feat_v = F.normalize(model.contra_head_v(model.pool_vision_for_contra(video_output)), dim=-1)
@@ -111,9 +113,17 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=
     feat_t = F.normalize(model.contra_head_t(model.pool_text_for_contra(caption_output)), dim=-1)
     sim_t2v = torch.matmul(feat_t, feat_v.permute(1, 0))
     video_input = model.get_multimodal_forward_input_vision(video_output)
-    video_input = video_input.expand(input_ids.shape[0], -1, -1).contiguous()
-    slice_output = model.forward_multimodal_encoder(input_ids, attention_mask, video_input).sequence_output
-    slice_scores = F.softmax(model.itm_head(slice_output[:, 0]), dim=1)[:, 1]
+    if rerank:
+        from mico_amd import runtime
+        from mico_amd.evaluation import rerank_retrieval
+        # every text's shortlist is the one image (k = 1): itm_scores [texts, 1] is the demo's score per text
+        res = rerank_retrieval(model, feat_t, input_ids, attention_mask, feat_v, video_input.to(runtime.compute_dtype()), k=1,
+                               directions=("t2c",))
+        slice_scores = res["t2c"]["itm_scores"][:, 0]
+    else:
+        video_input = video_input.expand(input_ids.shape[0], -1, -1).contiguous()
+        slice_output = model.forward_multimodal_encoder(input_ids, attention_mask, video_input).sequence_output
+        slice_scores = F.softmax(model.itm_head(slice_output[:, 0]), dim=1)[:, 1]
     # caption generation (inference_demo.py:161-174)
     cap_input = model.get_multimodal_forward_input_vision(video_output)
     tk = model.multimodal_encoder.tokenizer
@@ -135,6 +145,7 @@ def main():
     ap.add_argument("--texts", nargs="*", default=["a man is skiing in a snowy day.", "it's a hot day"])
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--use_cache", action="store_true", help="decode the caption incrementally (K/V cache; same caption)")
+    ap.add_argument("--rerank", action="store_true", help="ITM scores through the retrieval evaluation path (indexed K/V memory; same scores)")
     args = ap.parse_args()
     device = "cuda"
     from mico_amd import runtime
@@ -150,7 +161,7 @@ def main():
     image_input = proc(args.image)
     if image_input is None:
         raise SystemExit(f"cannot read {args.image}")
-    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache)
+    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache, rerank=args.rerank)
     print(out["sim_t2v"])
     print(out["itm_scores"])
     print(out["captions"])

@@ -38,6 +38,7 @@ class AttnParams(C.Structure):
         ("q_bs", c_i64), ("q_rs", c_i64), ("k_bs", c_i64), ("k_rs", c_i64), ("v_bs", c_i64), ("v_rs", c_i64),
         ("o_bs", c_i64), ("o_rs", c_i64), ("scale", c_f), ("mask", c_vp), ("mask_mode", c_int),
         ("drop_p", c_f), ("drop_seed", C.c_uint), ("drop_site", c_int), ("kv_batch_mod", c_int), ("batch0", c_int), ("dkv_accumulate", c_int),
+        ("kv_index", c_vp),
     ]
 
 
@@ -102,6 +103,7 @@ PROTOTYPES = {
     "mico_bert_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp],
     "mico_embed_scatter_add": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_f, c_vp],
     "mico_itm_sample": [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp],
+    "mico_topk_rows": [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp],
     "mico_token_mask": [c_vp, c_int, c_int, c_f, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp],
     "mico_win_attn_fwd": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f, c_int, c_vp],
     "mico_win_attn_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f, c_f, c_int, c_vp],
@@ -142,7 +144,7 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 116   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 117   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):

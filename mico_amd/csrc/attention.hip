@@ -178,7 +178,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const T* __restric
     const bool stager = NW == 4 || tid < 256;      // (wave-uniform)
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * (NW * 16 * RB);
     const T* qb = q + (int64_t)b * p.q_bs + h * p.hd;
-    const int kvb = p.kv_batch_mod > 0 ? b % p.kv_batch_mod : b;   // shared K/V memory (see mico_attn_params)
+    const int kvb = p.kv_index ? p.kv_index[b] : (p.kv_batch_mod > 0 ? b % p.kv_batch_mod : b);   // shared / indexed K/V memory (see mico_attn_params)
     const T* kb = k + (int64_t)kvb * p.k_bs + h * p.hd;
     const T* vb = v + (int64_t)kvb * p.v_bs + h * p.hd;
     const int i0 = q0 + wave * (16 * RB) + (lane & 15);   // this lane's query rows: i0 + rb * 16
@@ -2918,6 +2918,7 @@ int check_params(const mico_attn_params* p, const char* who) {
     MICO_CHECK(p->drop_p >= 0.f && p->drop_p < 1.f, "%s: drop_p must be in [0, 1)", who);
     MICO_CHECK(p->kv_batch_mod >= 0, "%s: kv_batch_mod must be >= 0", who);
     MICO_CHECK(p->batch0 >= 0, "%s: batch0 must be >= 0", who);
+    MICO_CHECK(!p->kv_index || p->kv_batch_mod == 0, "%s: kv_index and kv_batch_mod are two ways to name a batch entry's K/V set - give one", who);
     return MICO_OK;
 }
 
@@ -2946,7 +2947,8 @@ extern "C" int mico_attn_fwd(const void* q, const void* k, const void* v, void* 
     // two query blocks per wave beyond 64 query rows
     static const bool no_res = getenv("MICO_ATTN_NORES") != nullptr;   // A/B switch for tools/attn_bench.py, tools/probes/attn_phases.py
     // K/V-resident persistent kernel: unmasked self-attention of the ViT towers (hd 128 would spill next to the prefetch registers)
-    if (!no_res && p->kv_batch_mod == 0 && p->mask_mode == 0 && p->drop_p <= 0.f && p->hd <= 96 && p->k_rs == p->v_rs && p->Sq > 128 && p->Sk <= 272 && p->Sq <= 256 + ResCfg<96>::NXMAX) {
+    // (a kv_index table, like kv_batch_mod, keeps the launch on the tiled kernel: the resident kernels address K / V by the batch entry)
+    if (!no_res && p->kv_batch_mod == 0 && !p->kv_index && p->mask_mode == 0 && p->drop_p <= 0.f && p->hd <= 96 && p->k_rs == p->v_rs && p->Sq > 128 && p->Sk <= 272 && p->Sq <= 256 + ResCfg<96>::NXMAX) {
         static const int n_cu = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
         const int nitems = p->B * p->H;
         const dim3 grid(nitems < n_cu ? nitems : n_cu);
@@ -2989,6 +2991,7 @@ extern "C" int mico_attn_bwd(const void* q, const void* k, const void* v, const 
     MICO_CHECK(dtype_ok(dtype) && q && k && v && o && d_o && lse && dq && dk && dv && delta, "mico_attn_bwd: bad args");
     int rc = check_params(p, "mico_attn_bwd");
     if (rc) return rc;
+    MICO_CHECK(!p->kv_index, "mico_attn_bwd: kv_index is an inference feature of mico_attn_fwd (dK / dV of an indexed K/V memory would need a scatter-add)");
     hipStream_t st = (hipStream_t)stream;
     const dim3 block(256);
     // short query sequences at hd 64 (BERT's self- and cross-attention): the fused one-pass kernel

@@ -3537,7 +3537,7 @@ static constexpr int g_mico_gemm_variant = 0;
 static constexpr int g_mico_mid_group = 0;
 #endif
 extern "C" int mico_gemm_last_kernel(void) { return g_mico_last_gemm_kernel; }
-extern "C" int mico_version(void) { return 116; }
+extern "C" int mico_version(void) { return 117; }
 extern "C" const char* mico_last_error_string(void) { return g_mico_err; }
 
 extern "C" int mico_struct_layout(int* out, int n) {
@@ -3559,6 +3559,7 @@ extern "C" int mico_struct_layout(int* out, int n) {
         OFF(mico_attn_params, v_rs), OFF(mico_attn_params, o_bs), OFF(mico_attn_params, o_rs), OFF(mico_attn_params, scale), OFF(mico_attn_params, mask),
         OFF(mico_attn_params, mask_mode), OFF(mico_attn_params, drop_p), OFF(mico_attn_params, drop_seed), OFF(mico_attn_params, drop_site),
         OFF(mico_attn_params, kv_batch_mod), OFF(mico_attn_params, batch0), OFF(mico_attn_params, dkv_accumulate),
+        OFF(mico_attn_params, kv_index),
         -1,
         (int)sizeof(mico_ln_fwd_params),
         OFF(mico_ln_fwd_params, x), OFF(mico_ln_fwd_params, x_dtype), OFF(mico_ln_fwd_params, x_normalized), OFF(mico_ln_fwd_params, gamma),

@@ -107,6 +107,90 @@ __global__ __launch_bounds__(64) void itm_sample_kernel(const float* __restrict_
     }
 }
 
+// Row-wise top-k (mico_topk_rows): one wave per row, ONE pass over the row.  Every element becomes a 64-bit key - the value's bits made
+// monotonic in the high word, ~column in the low word - so the order is total: larger value first, equal values by ascending column, NaN last.
+// The wave keeps the best TOPK_MAX keys seen so far sorted in LDS next to a staging area of the same size; an element enters the staging area only
+// if its key beats the current k-th best (for a random row that happens ~k ln(cols / k) times in all), and a full staging area is folded in by a
+// 256-key bitonic sort.  A row sorted ascending is the worst case: a sort per 65 .. 128 elements.
+constexpr int TOPK_MAX = 128;
+
+__device__ __forceinline__ unsigned long long topk_key(float v, int col) {
+    v += 0.f;                                           // -0 -> +0: equal values tie-break by column
+    unsigned u = __float_as_uint(v);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // monotonic in the value
+    if (v != v) u = 0u;                                 // NaN below -inf
+    return ((unsigned long long)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)col);
+}
+
+__device__ __forceinline__ void topk_sort256(unsigned long long* buf, int lane) {   // descending; one wave; 36 compare-exchange steps, fully
+#pragma unroll                                                                      // unrolled: every stride and direction mask is a constant
+    for (int size = 2; size <= 2 * TOPK_MAX; size <<= 1) {
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int t = lane + r * 64;
+                const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+                const unsigned long long a = buf[lo], b = buf[hi];
+                const bool desc = (lo & size) == 0;
+                if (desc ? a < b : a > b) { buf[lo] = b; buf[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void topk_rows_kernel(const float* __restrict__ sim, int64_t ld, int cols, int k, int* __restrict__ idx_out,
+                                                       float* __restrict__ val_out) {
+    __shared__ unsigned long long buf[2 * TOPK_MAX];    // [0, TOPK_MAX): best so far, sorted; [TOPK_MAX, 2 TOPK_MAX): staging
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const float* x = sim + (int64_t)row * ld;
+    for (int i = lane; i < 2 * TOPK_MAX; i += 64) buf[i] = 0ull;   // 0 is below every real key
+    __syncthreads();
+    unsigned long long thr = 0ull;
+    int cnt = 0;                                        // staged keys (wave-uniform)
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    float cur[4], nxt[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const int c = j * 64 + lane; cur[j] = c < cols ? x[c] : 0.f; }
+    for (int c0 = 0; c0 < cols; c0 += 256) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int c = c0 + 256 + j * 64 + lane; nxt[j] = c < cols ? x[c] : 0.f; }   // next block in flight
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j * 64 + lane;
+            if (c0 + j * 64 >= cols) break;             // (wave-uniform)
+            if (cnt > TOPK_MAX - 64) {                  // the next 64 elements might not fit: fold the staging area in
+                for (int i = cnt + lane; i < TOPK_MAX; i += 64) buf[TOPK_MAX + i] = 0ull;
+                __syncthreads();
+                topk_sort256(buf, lane);
+                thr = buf[k - 1];
+                cnt = 0;
+                __syncthreads();
+            }
+            const unsigned long long key = topk_key(cur[j], c);
+            const bool pass = c < cols && key > thr;
+            const unsigned long long m = __ballot(pass);
+            if (pass) buf[TOPK_MAX + cnt + __popcll(m & lt_mask)] = key;
+            cnt += __popcll(m);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cur[j] = nxt[j];
+    }
+    if (cnt > 0) {
+        for (int i = cnt + lane; i < TOPK_MAX; i += 64) buf[TOPK_MAX + i] = 0ull;
+        __syncthreads();
+        topk_sort256(buf, lane);
+    }
+    __syncthreads();
+    for (int i = lane; i < k; i += 64) {
+        const unsigned long long key = buf[i];
+        const unsigned o = (unsigned)(key >> 32);
+        idx_out[(int64_t)row * k + i] = (int)(0xFFFFFFFFu - (unsigned)key);
+        if (val_out) val_out[(int64_t)row * k + i] = __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+    }
+}
+
 }  // namespace
 
 // TokenMasker.perform_mask (data/model/general_module.py:64-97) with the random numbers supplied by the caller: one wave per row.
@@ -188,6 +272,15 @@ extern "C" int mico_itm_sample(const float* sim, int64_t ld, int rows, int cols,
     MICO_CHECK(sim && u && out && cols > 0 && ld >= cols, "mico_itm_sample: bad args");
     if (rows <= 0) return MICO_OK;
     MICO_LAUNCH(itm_sample_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, sim, ld, cols, diag_offset, u, out);
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_topk_rows(const float* sim, int64_t row_stride, int rows, int cols, int k, int* idx_out, float* val_out, void* stream) {
+    MICO_CHECK(sim && idx_out && cols > 0 && row_stride >= cols, "mico_topk_rows: bad args");
+    MICO_CHECK(k >= 1 && k <= TOPK_MAX && k <= cols, "mico_topk_rows: k must be in [1, %d] and <= cols (got k = %d, cols = %d)", TOPK_MAX, k, cols);
+    if (rows <= 0) return MICO_OK;
+    MICO_LAUNCH(topk_rows_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, sim, row_stride, cols, k, idx_out, val_out);
     MICO_LAUNCH_CHECK();
     return MICO_OK;
 }

@@ -1603,6 +1603,23 @@ def _kv_layers(t2d, L, D):
     return t2d.view(t2d.shape[0], L, 2 * D).permute(1, 0, 2)
 
 
+def cross_kv_memory(spec, cond, kvparams):
+    """Inference form of CrossKVFn: the interleaved cross-attention K/V memory [n E, L * 2 D] of the condition tokens cond [n, E, D] for all
+    layers, in one GEMM.  cond in the compute dtype is read as it is (an evaluation keeps its candidates' tokens in 16 bits); fp32 is cast.
+    No autograd, no DkvSession.  kvparams: per layer key.weight, key.bias, value.weight, value.bias."""
+    dt = runtime.compute_dtype()
+    n, E, D = cond.shape
+    c2 = cond.detach().contiguous().view(n * E, D)
+    if c2.dtype == torch.float32:
+        c2 = ops.cast_f32_to_16(c2, _empty((n * E, D), dt, cond.device))
+    elif c2.dtype != dt:
+        raise ops.MicoHipError(f"condition tokens are {c2.dtype}, the compute dtype is {dt}")
+    L = spec.L
+    kvbuf = _empty((n * E, L * 2 * D), dt, cond.device)
+    _fwd_gemm(c2, "bkv_all", _kv_all_weights(kvparams, L), kvbuf, bias=torch.cat([kvparams[4 * li + j].detach() for li in range(L) for j in (1, 3)]))
+    return kvbuf
+
+
 class DkvSession:
     """One per shared cross-attention K/V memory (BertModel.project_cross_kv attaches it to kv_own): the BERT passes of a step that read the same
     own set - the ITM triplet and the captioning pass - put its 16-bit gradient into ONE [n E, L * 2 D] buffer.  The first BertFn.backward of
@@ -1743,11 +1760,14 @@ class BertFn(torch.autograd.Function):
         n entries reads kv_own, one of 3 n entries is the ITM triplet [own | neg | own] and reads [kv_own | kv_neg] modulo 2 n.
         drop: None (eval), (p_hidden, p_attention, seed) - train-mode dropout of bert.py:148,267,295,373 - or a dict
         {"kv_cache": {...}} (inference only): the per-layer cross-attention K/V projections of `cond` are stored in / taken from
-        that dict, so a decode loop projects its (constant) condition tokens once instead of at every step."""
+        that dict, so a decode loop projects its (constant) condition tokens once instead of at every step; or a dict
+        {"kv_index": int32 [b], "kv_sets": n} (inference only, with the 2-D kv_own of cross_kv_memory holding n sets): batch entry i
+        attends to set kv_index[i] (mico_attn_params.kv_index) - retrieval re-ranking, where every candidate is projected once."""
         runtime.remember_precision(ctx)
-        kv_cache = None
+        kv_cache = kv_index = None
+        kv_sets = 0
         if isinstance(drop, dict):
-            kv_cache, drop = drop["kv_cache"], None
+            kv_cache, kv_index, kv_sets, drop = drop.get("kv_cache"), drop.get("kv_index"), int(drop.get("kv_sets", 0)), None
         dt = runtime.compute_dtype()
         ph, pa, dseed = drop if drop is not None else (0.0, 0.0, 0)
         hd_drop = (lambda site: (ph, dseed, site)) if ph > 0 else (lambda site: None)
@@ -1774,6 +1794,9 @@ class BertFn(torch.autograd.Function):
         if kv_own is not None:
             assert cond is None and kv_cache is None
             n_own = b if kv_neg is None else b // 3
+            if kv_index is not None:
+                assert kv_neg is None and kv_own.dim() == 2 and kv_sets > 0 and kv_own.shape[0] % kv_sets == 0
+                n_own = kv_sets
             kv_2d = kv_own.dim() == 2        # the interleaved memory: [n E, L * 2 D] row-major (CrossKVFn), read per layer through its row stride
             if kv_2d:
                 assert kv_own.is_contiguous() and kv_own.shape[1] == spec.L * 2 * D
@@ -1840,7 +1863,7 @@ class BertFn(torch.autograd.Function):
                 krs = kv.stride(0)       # 2 D, or L * 2 D for a layer of the interleaved shared memory (CrossKVFn)
                 stc = dict(q_strides=(S * D, D), k_strides=(E * krs, krs), v_strides=(E * krs, krs), o_strides=(S * D, D))
                 ops.attn_fwd(q, kv, kv[:, D:], cc, lse_c, B=b, H=H, Sq=S, Sk=E, hd=hd, scale=scale, mask=None,
-                             drop=at_drop(li * 8 + SITE_CROSS_P), kv_batch_mod=kv_mod, **stc)
+                             drop=at_drop(li * 8 + SITE_CROSS_P), kv_batch_mod=kv_mod, kv_index=kv_index, **stc)
                 u2 = _empty((rows, D), torch.float32, dev)
                 _fwd_gemm(cc, "w1", [P(p + "crossattention.output.dense.weight")], u2,
                           bias=P(p + "crossattention.output.dense.bias"), resid=x32, drop=hd_drop(li * 8 + SITE_CROSS_OUT))
@@ -1856,7 +1879,8 @@ class BertFn(torch.autograd.Function):
                       drop=hd_drop(li * 8 + SITE_FFN_OUT))
             x32, x16, m3, r3 = ln_out(u3, p + "output.")
             a.update(h=h, act=act, u3=u3, m3=m3, r3=r3)
-            acts.append(a)
+            if kv_index is None:      # (an indexed pass is inference by contract: a layer's activations are dropped as soon as the next one has read them)
+                acts.append(a)
         ctx.spec, ctx.params, ctx.acts, ctx.dt = spec, params, acts, dt
         ctx.misc = (ids, emb, mean_e, rstd_e, cond16, mask, b, S, E)
         ctx.drop = drop

@@ -106,12 +106,16 @@ class BertModel(nn.Module):
     def project_cross_kv(self, cond_own, cond_neg=None):
         """Cross-attention K/V memory of condition tokens for all layers, to be shared by several passes of one training step
         (`cross_kv=` of forward): (kv_own, kv_neg) for the batch's own tokens [b, E, D] and, optionally, ITM hard negatives.
-        Differentiable with respect to the tokens and the key / value projections (functional.CrossKVFn)."""
+        Differentiable with respect to the tokens and the key / value projections (functional.CrossKVFn).
+        Without grad (evaluation): no autograd node and no gradient session; cond_own may be 16-bit (the compute dtype) and kv_own is the
+        interleaved [b E, L 2 D] memory that forward(cross_kv=kv_own, kv_index=...) reads by index."""
         spec, params = self._bert_spec()
         kvp = []
         for li in range(spec.L):
             ca = f"encoder.layer.{li}.crossattention.self."
             kvp += [params[spec.idx[ca + n]] for n in ("key.weight", "key.bias", "value.weight", "value.bias")]
+        if not torch.is_grad_enabled() and cond_neg is None:
+            return Fn.cross_kv_memory(spec, cond_own, kvp), None
         session = Fn.DkvSession()
         kv_own, kv_neg = Fn.CrossKVFn.apply(spec, session, cond_own, cond_neg, *kvp)
         if kv_own.requires_grad:
@@ -119,8 +123,12 @@ class BertModel(nn.Module):
             kv_own._mico_dkv = session
         return kv_own, kv_neg
 
-    def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, kv_cache=None, cross_kv=None, **_):
-        """kv_cache (dict, inference only): holds the cross-attention K/V projections of `encoder_hidden_states` across calls -
+    def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, kv_cache=None, cross_kv=None, kv_index=None,
+                kv_sets=None, **_):
+        """kv_index (int32 [b], inference only) with cross_kv = the interleaved K/V memory of project_cross_kv under no_grad, [sets E, L 2 D]
+        (kv_sets = sets) or viewed [sets, E, L 2 D]: batch entry i attends to set kv_index[i], so b is independent of the number of sets
+        (retrieval re-ranking: every candidate projected once, read by all its pairs).  The values must lie in [0, sets).
+        kv_cache (dict, inference only): holds the cross-attention K/V projections of `encoder_hidden_states` across calls -
         the caller guarantees the condition tokens do not change between the calls that share the dict.
         cross_kv (training): (kv_own, kv_neg) from project_cross_kv instead of encoder_hidden_states; a batch of b entries attends
         to kv_own, a batch of 3 b entries is the ITM triplet [own | hard negative | own] and needs kv_neg as well."""
@@ -143,9 +151,23 @@ class BertModel(nn.Module):
         if cross_kv is not None:
             if encoder_hidden_states is not None or kv_cache is not None:
                 raise ValueError("cross_kv replaces encoder_hidden_states / kv_cache")
-            kv_own, kv_neg = cross_kv
+            kv_own, kv_neg = cross_kv if isinstance(cross_kv, (tuple, list)) else (cross_kv, None)
+            if kv_index is not None:
+                if torch.is_grad_enabled():
+                    raise RuntimeError("kv_index is an inference feature (the indexed K/V memory has no backward): call under torch.no_grad()")
+                if kv_neg is not None:
+                    raise ValueError("kv_index reads one K/V memory: cross_kv is a single tensor")
+                if kv_own.dim() == 3:
+                    kv_sets, kv_own = kv_own.shape[0], kv_own.reshape(-1, kv_own.shape[-1])
+                if not kv_sets or kv_own.dim() != 2 or kv_own.shape[0] % int(kv_sets):
+                    raise ValueError("kv_index needs cross_kv as [sets, E, L 2 D], or as [sets E, L 2 D] with kv_sets=sets")
+                if kv_index.dtype != torch.int32 or kv_index.shape != (input_ids.shape[0],):
+                    raise ValueError("kv_index is an int32 [batch] tensor")
+                drop = {"kv_index": kv_index.contiguous(), "kv_sets": int(kv_sets)}
             if kv_neg is not None and input_ids.shape[0] % 3:
                 raise ValueError("cross_kv with hard negatives expects the ITM triplet batch [own | negative | own]")
+        elif kv_index is not None:
+            raise ValueError("kv_index needs cross_kv")
         seq = Fn.BertFn.apply(spec, input_ids, extended_attention_mask(attention_mask), encoder_hidden_states, drop, kv_own, kv_neg,
                               *params)
         return _Out(last_hidden_state=seq)

@@ -329,9 +329,13 @@ def attn_bwd_smallq_ok(B, H, Sq, Sk, hd, drop=None, batch0=0):
 
 
 def _attn_params(B, H, Sq, Sk, hd, q, k, v, o, scale, mask, q_strides, k_strides, v_strides, o_strides, drop=None, kv_batch_mod=0, batch0=0,
-                 dkv_accumulate=False):
+                 dkv_accumulate=False, kv_index=None):
     p = AttnParams()
     p.kv_batch_mod = int(kv_batch_mod)
+    if kv_index is not None:
+        if kv_index.dtype != torch.int32 or kv_index.dim() != 1 or kv_index.numel() != B or not kv_index.is_contiguous():
+            raise MicoHipError(f"kv_index is a contiguous int32 [B = {B}] device tensor (got {kv_index.dtype} {tuple(kv_index.shape)})")
+        p.kv_index = _p(kv_index)
     p.batch0, p.dkv_accumulate = int(batch0), int(bool(dkv_accumulate))
     if drop is not None:
         p.drop_p, p.drop_seed, p.drop_site = float(drop[0]), int(drop[1]) & 0xFFFFFFFF, int(drop[2])
@@ -352,10 +356,11 @@ def _attn_params(B, H, Sq, Sk, hd, q, k, v, o, scale, mask, q_strides, k_strides
 
 
 def attn_fwd(q, k, v, o, lse, *, B, H, Sq, Sk, hd, scale, mask=None, q_strides, k_strides, v_strides, o_strides, drop=None,
-             kv_batch_mod=0):
+             kv_batch_mod=0, kv_index=None):
     """q/k/v/o are 16-bit tensors (possibly views into one fused projection buffer); *_strides = (batch, row) in
-    elements.  mask: additive fp32 [B,Sk] or [B,Sq,Sk]."""
-    p = _attn_params(B, H, Sq, Sk, hd, q, k, v, o, scale, mask, q_strides, k_strides, v_strides, o_strides, drop, kv_batch_mod)
+    elements.  mask: additive fp32 [B,Sk] or [B,Sq,Sk].  kv_index (inference): int32 [B] device tensor - batch entry b reads the K/V set
+    kv_index[b] (k_strides[0] / v_strides[0] apart); the caller guarantees every value names a set the buffers hold (mico_attn_params.kv_index)."""
+    p = _attn_params(B, H, Sq, Sk, hd, q, k, v, o, scale, mask, q_strides, k_strides, v_strides, o_strides, drop, kv_batch_mod, kv_index=kv_index)
     rc = _lib.lib().mico_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), C.byref(p), dt_code(q.dtype), _st())
     check(rc, "mico_attn_fwd")
 
@@ -410,10 +415,11 @@ def decode_kv_gather(src, dst, parent, n):
 
 
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, delta, *, B, H, Sq, Sk, hd, scale, mask=None, q_strides, k_strides,
-             v_strides, o_strides, drop=None, kv_batch_mod=0, batch0=0, dkv_accumulate=False):
+             v_strides, o_strides, drop=None, kv_batch_mod=0, batch0=0, dkv_accumulate=False, kv_index=None):
     """kv_batch_mod > 0: k / v hold kv_batch_mod batch entries shared modulo (see mico_attn_params); dk / dv are [B, ...] as always.
     batch0: this launch covers entries batch0 .. batch0 + B of a larger batch (dropout counters); dkv_accumulate: dk / dv += (short-query kernel)."""
-    p = _attn_params(B, H, Sq, Sk, hd, q, k, v, o, scale, mask, q_strides, k_strides, v_strides, o_strides, drop, kv_batch_mod, batch0, dkv_accumulate)
+    p = _attn_params(B, H, Sq, Sk, hd, q, k, v, o, scale, mask, q_strides, k_strides, v_strides, o_strides, drop, kv_batch_mod, batch0, dkv_accumulate,
+                     kv_index=kv_index)      # (kv_index: refused by the library - the forward's inference-only indexed K/V has no backward)
     rc = _lib.lib().mico_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(dq), _p(dk), _p(dv), _p(delta),
                                   C.byref(p), dt_code(q.dtype), _st())
     check(rc, "mico_attn_bwd")
@@ -585,6 +591,27 @@ def itm_sample(sim, diag_offset, u):
     check(_lib.lib().mico_itm_sample(_p(sim), sim.stride(0), sim.shape[0], sim.shape[1], int(diag_offset), _p(u.contiguous()), _p(out), _st()),
           "mico_itm_sample")
     return out
+
+
+TOPK_MAX = 128   # largest k of mico_topk_rows (TOPK_MAX in csrc/loss.hip)
+
+
+def topk_rows(sim, k):
+    """(values fp32 [rows, k], indices int32 [rows, k]) - the k largest entries of every row of the fp32 matrix `sim` in descending order, equal
+    values by ascending column (mico_topk_rows: one pass over the matrix, no sort workspace).  1 <= k <= min(TOPK_MAX, cols)."""
+    if sim.dim() != 2 or sim.dtype != torch.float32:
+        raise MicoHipError(f"topk_rows takes a 2-D fp32 matrix (got {sim.dtype} {tuple(sim.shape)})")
+    if sim.stride(1) != 1:
+        sim = sim.contiguous()
+    rows, cols = sim.shape
+    idx = torch.empty((rows, int(k)), dtype=torch.int32, device=sim.device)
+    val = torch.empty((rows, int(k)), dtype=torch.float32, device=sim.device)
+    if rows == 0:
+        if not sim.is_cuda:
+            _p(sim)
+        return val, idx
+    check(_lib.lib().mico_topk_rows(_p(sim), sim.stride(0) if rows > 1 else cols, rows, cols, int(k), _p(idx), _p(val), _st()), "mico_topk_rows")
+    return val, idx
 
 
 def win_attn_fwd(qkv, out, lse, bias_table, batch, res, heads, shift, scale):

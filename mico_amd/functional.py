@@ -1593,9 +1593,21 @@ def _fwd_gemm(x, key, plist, out, **kw):
 SITE_SELF_OUT, SITE_CROSS_OUT, SITE_FFN_OUT, SITE_SELF_P, SITE_CROSS_P, SITE_EMB = 0, 1, 2, 3, 4, 100000
 
 
-def _kv_all_weights(kvparams, L):
-    """key.weight, value.weight of every layer in order: the rows of the [L * 2 D, D] weight behind the interleaved K/V memory."""
-    return [kvparams[4 * li + j] for li in range(L) for j in (0, 2)]
+def cross_kv_params(spec, params):
+    """Per layer key.weight, key.bias, value.weight, value.bias of the cross-attention, out of BertModel's parameters in spec order."""
+    return [params[spec.idx[f"encoder.layer.{li}.crossattention.self.{n}"]] for li in range(spec.L)
+            for n in ("key.weight", "key.bias", "value.weight", "value.bias")]
+
+
+def _kv_all(kvparams, L):
+    """(weight-cache key, [key.weight, value.weight of every layer in order]): the [L * 2 D, D] weight behind the shared K/V memory."""
+    return "bkv_all", [kvparams[4 * li + j] for li in range(L) for j in (0, 2)]
+
+
+def _project_kv_all(x16, kvparams, L, out):
+    """out [rows, L * 2 D] = every layer's cross-attention K | V of the 16-bit tokens x16 [rows, D], in one GEMM (N = L * 2 D)."""
+    key, weights = _kv_all(kvparams, L)
+    return _fwd_gemm(x16, key, weights, out, bias=torch.cat([kvparams[4 * li + j].detach() for li in range(L) for j in (1, 3)]))
 
 
 def _kv_layers(t2d, L, D):
@@ -1614,9 +1626,8 @@ def cross_kv_memory(spec, cond, kvparams):
         c2 = ops.cast_f32_to_16(c2, _empty((n * E, D), dt, cond.device))
     elif c2.dtype != dt:
         raise ops.MicoHipError(f"condition tokens are {c2.dtype}, the compute dtype is {dt}")
-    L = spec.L
-    kvbuf = _empty((n * E, L * 2 * D), dt, cond.device)
-    _fwd_gemm(c2, "bkv_all", _kv_all_weights(kvparams, L), kvbuf, bias=torch.cat([kvparams[4 * li + j].detach() for li in range(L) for j in (1, 3)]))
+    kvbuf = _empty((n * E, spec.L * 2 * D), dt, cond.device)
+    _project_kv_all(c2, kvparams, spec.L, kvbuf)
     return kvbuf
 
 
@@ -1643,10 +1654,9 @@ class CrossKVFn(torch.autograd.Function):
     that attends to the same tokens with the same weights: the ITM triplet [own | hard negative | own] (vast.py:438-447) contains
     the batch's own condition tokens twice and the captioning pass (vast.py:486-512) a third time - the reference projects them in
     every pass (bert.py:206-215).  Returns (kv_own, kv_neg): 16-bit views of ONE buffer whose rows are [own | neg], so that a BERT pass over the
-    triplet reads it through mico_attn_params.kv_batch_mod.  Memory layout (runtime.CFG.kv_interleaved, default): [rows][L][K | V], handed out as
-    2-D [n E, L * 2 D] tensors - a layer is a column block with row stride L * 2 D, every layer's projection one GEMM, and the backward one product
-    over K = L * 2 D for the condition-token gradient; or [L][rows][K | V] (3-D [L][n E, 2 D] views) with a launch per layer (fp32 accumulation
-    into the token gradient 12 times).
+    triplet reads it through mico_attn_params.kv_batch_mod.  Memory layout: [rows][L][K | V], handed out as 2-D [n E, L * 2 D] tensors - a layer
+    is a column block with row stride L * 2 D, every layer's projection one GEMM, and the backward one product over K = L * 2 D for the
+    condition-token gradient.
     The gradients handed back by BertFn for these two outputs stay in the engine's 16-bit gradient scale (runtime.grad_scale());
     this function removes it - the one place where a scaled gradient crosses autograd, between two of our own functions."""
 
@@ -1665,25 +1675,13 @@ class CrossKVFn(torch.autograd.Function):
         ops.cast_f32_to_16(cond_own.contiguous().view(n * E, D), cond16[:n * E])
         if cond_neg is not None:
             ops.cast_f32_to_16(cond_neg.contiguous().view(n * E, D), cond16[n * E:])
-        L = spec.L
-        ctx.interleaved = bool(runtime.CFG.kv_interleaved)
-        if ctx.interleaved:
-            # [rows][layer][K | V]: every layer's projection in one launch (N = L * 2 D); a layer is the view kv[li] with row stride L * 2 D
-            kvbuf = _empty((sets * n * E, L * 2 * D), dt, dev)
-            _fwd_gemm(cond16, "bkv_all", _kv_all_weights(kvparams, L), kvbuf, bias=torch.cat([kvparams[4 * li + j].detach() for li in range(L) for j in (1, 3)]))
-            kv = None
-        else:
-            kv = _empty((L, sets * n * E, 2 * D), dt, dev)
-            for li in range(L):
-                wk, bk, wv, bv = kvparams[4 * li: 4 * li + 4]
-                _fwd_gemm(cond16, "bkv", [wk, wv], kv[li], bias=torch.cat((bk.detach(), bv.detach())))
+        # [rows][layer][K | V]: every layer's projection in one launch (N = L * 2 D); a layer is a column block with row stride L * 2 D
+        kvbuf = _empty((sets * n * E, spec.L * 2 * D), dt, dev)
+        _project_kv_all(cond16, kvparams, spec.L, kvbuf)
         ctx.spec, ctx.kvparams, ctx.cond16, ctx.shape, ctx.sets = spec, kvparams, cond16, (n, E, D), sets
         ctx.needs = (cond_own.requires_grad, cond_neg is not None and cond_neg.requires_grad)
-        if ctx.interleaved:      # 2-D [rows, L * 2 D]: contiguous row blocks (so are their gradients: autograd's sums over the passes stay on its fast path)
-            return (kvbuf[:n * E], kvbuf[n * E:]) if sets == 2 else (kvbuf, None)
-        if sets == 2:
-            return kv[:, :n * E], kv[:, n * E:]
-        return kv, None
+        # contiguous row blocks (so are their gradients: autograd's sums over the passes stay on its fast path)
+        return (kvbuf[:n * E], kvbuf[n * E:]) if sets == 2 else (kvbuf, None)
 
     @staticmethod
     @runtime.saved_precision
@@ -1708,66 +1706,200 @@ class CrossKVFn(torch.autograd.Function):
         if ctx.sets == 2:
             parts.append((dkv_neg, cond16[n * E:]))
         L = spec.L
-        if ctx.interleaved:
-            # the gradients arrived in the forward's layout ([rows][layer][dK | dV], BertFn writes them so and autograd's sums keep it): all layers
-            # at once - dW [L * 2 D, D] in one launch per set, the condition-token gradient as ONE product over K = L * 2 D
-            CrossKVFn.concat_backwards += 1
-            wall = _fused_w("bkv_all", _kv_all_weights(kvparams, L))
-            dw = torch.zeros((L * 2 * D, D), dtype=torch.float32, device=dev)
-            db = torch.zeros(L * 2 * D, dtype=torch.float32, device=dev)
-            dconds = [None, None]
-            for pi, (dkv, c16) in enumerate(parts):
-                if dkv is None:
-                    continue
-                d2 = dkv if (dkv.stride(1) == 1 and dkv.stride(0) % 8 == 0) else dkv.contiguous()      # [n E, L * 2 D]
-                # (the weight-gradient kernels address a reduction-major operand with 32-bit byte offsets from its first row: row chunks of < 4 GiB)
-                rmax = max(64, (0xF0000000 // (L * 2 * D * d2.element_size())) // 64 * 64)
-                for r0 in range(0, n * E, rmax):
-                    linear_wgrad(d2[r0:r0 + rmax], c16[r0:r0 + rmax], dw, inv_s, dbias=db)
-                if ctx.needs[pi]:
-                    dconds[pi] = _empty((n * E, D), torch.float32, dev)
-                    ops.gemm(d2, wall, dconds[pi], tb=True, M=n * E, N=D, K=L * 2 * D, alpha=inv_s)
-            grads = []
-            for li in range(L):
-                r0 = li * 2 * D
-                grads += [dw[r0:r0 + D], db[r0:r0 + D], dw[r0 + D:r0 + 2 * D], db[r0 + D:r0 + 2 * D]]
-            dc = [d.view(n, E, D) if d is not None else None for d in dconds]
-            return (None, None, dc[0], dc[1]) + tuple(grads)
-        dconds = [torch.zeros((n * E, D), dtype=torch.float32, device=dev) if (need and d is not None) else None
-                  for need, (d, _) in zip(ctx.needs, parts)] + [None] * (2 - len(parts))
+        # the gradients arrived in the forward's layout ([rows][layer][dK | dV], BertFn writes them so and autograd's sums keep it): all layers
+        # at once - dW [L * 2 D, D] in one launch per set, the condition-token gradient as ONE product over K = L * 2 D
+        CrossKVFn.concat_backwards += 1
+        wall = _fused_w(*_kv_all(kvparams, L))
+        dw = torch.zeros((L * 2 * D, D), dtype=torch.float32, device=dev)
+        db = torch.zeros(L * 2 * D, dtype=torch.float32, device=dev)
+        dconds = [None, None]
+        for pi, (dkv, c16) in enumerate(parts):
+            if dkv is None:
+                continue
+            d2 = dkv if (dkv.stride(1) == 1 and dkv.stride(0) % 8 == 0) else dkv.contiguous()      # [n E, L * 2 D]
+            # (the weight-gradient kernels address a reduction-major operand with 32-bit byte offsets from its first row: row chunks of < 4 GiB)
+            rmax = max(64, (0xF0000000 // (L * 2 * D * d2.element_size())) // 64 * 64)
+            for r0 in range(0, n * E, rmax):
+                linear_wgrad(d2[r0:r0 + rmax], c16[r0:r0 + rmax], dw, inv_s, dbias=db)
+            if ctx.needs[pi]:
+                dconds[pi] = _empty((n * E, D), torch.float32, dev)
+                ops.gemm(d2, wall, dconds[pi], tb=True, M=n * E, N=D, K=L * 2 * D, alpha=inv_s)
         grads = []
-        for li in range(spec.L):
-            wk, bk, wv, bv = kvparams[4 * li: 4 * li + 4]
-            dw = torch.zeros((2 * D, D), dtype=torch.float32, device=dev)
-            db = torch.zeros(2 * D, dtype=torch.float32, device=dev)
-            for pi, (dkv, c16) in enumerate(parts):
-                if dkv is None:
-                    continue
-                d = dkv[li]
-                linear_wgrad(d, c16, dw, inv_s)
-                ops.colsum(d, db, scale=inv_s, accumulate=True)
-                if dconds[pi] is not None:
-                    ops.gemm(d, _fused_w("bkv", [wk, wv]), dconds[pi], tb=True, M=n * E, N=D, K=2 * D, alpha=inv_s, accumulate=True)
-            grads += [dw[:D], db[:D], dw[D:], db[D:]]
+        for li in range(L):
+            r0 = li * 2 * D
+            grads += [dw[r0:r0 + D], db[r0:r0 + D], dw[r0 + D:r0 + 2 * D], db[r0 + D:r0 + 2 * D]]
         dc = [d.view(n, E, D) if d is not None else None for d in dconds]
         return (None, None, dc[0], dc[1]) + tuple(grads)
 
 
+class _SharedDkv:
+    """The dK / dV of one BertFn.backward over a shared K/V memory (CrossKVFn), in the 16-bit gradient scale (CrossKVFn.backward removes it):
+    which buffers they go to, a layer's cross-attention backward in the launches that fill them, and what autograd and the DkvSession get.
+      own set only       (captioning pass) one launch per layer into the own buffer [n E, L * 2 D];
+      ITM triplet        [own | neg | own]: [own | neg] are adjacent row blocks of ONE buffer - batch entries [0, 2 n) write their rows straight
+                         into the pair, the third third ADDS onto the own half in a second launch: no per-entry buffer, no add / copy passes.
+                         Without the short-query kernel (the only one that adds): one launch into a per-entry buffer, folded by add / copy_;
+      session            (DkvSession: the passes that read one own set share ONE gradient buffer for it) an earlier backward of this pass
+                         registered its own buffer: this one adds to it in the attention kernel - a triplet in three launches, its negatives
+                         into a buffer of their own - and hands autograd None for kv_own."""
+
+    def __init__(self, session, spec, b, S, E, has_neg, drop, dt, dev):
+        """session: kv_own's DkvSession, or None (none attached, or the engine does not ask for kv_own's gradient); drop: the dropout spec of a
+        cross-attention site or None (its probability decides which kernel the library takes, the site does not)."""
+        L, D = spec.L, spec.D
+        n = b // 3 if has_neg else b
+        self.b, self.n, self.S, self.E, self.D, self.H, self.has_neg, self.dt = b, n, S, E, D, spec.H, has_neg, dt
+        # the launches that add (the triplet's last third; every launch onto a session's buffer) need the short-query kernel for their shape
+        self.smallq = ops.attn_bwd_smallq_ok(n, spec.H, S, E, D // spec.H, drop, batch0=2 * n if has_neg else 0)
+        # (a session only under an engine that can tell backward passes apart - the condition GradArena.session has: without it, a buffer per pass)
+        self.sess = session if (runtime.CFG.dkv_inplace and hasattr(torch._C, "_current_graph_task_id")) else None
+        self.acc = False      # the own set's dK / dV are added to the buffer an earlier backward of this pass registered
+        sess = self.sess
+        if sess is not None and sess.own is not None and not sess.closed:
+            if self.smallq and tuple(sess.own.shape) == (n * E, L * 2 * D) and sess.own.dtype == dt:
+                self.acc = True
+            else:
+                sess.closed = True
+        self.pair = None
+        if self.acc:          # (the triplet's hard negatives: only this pass reads them)
+            self.own2d, self.neg2d = sess.own, _empty((n * E, L * 2 * D), dt, dev) if has_neg else None
+        elif has_neg:
+            pair = _empty((2 * n * E, L * 2 * D), dt, dev)
+            self.own2d, self.neg2d, self.pair = pair[:n * E], pair[n * E:], _kv_layers(pair, L, D)
+        else:
+            self.own2d, self.neg2d = _empty((n * E, L * 2 * D), dt, dev), None
+        self.own = _kv_layers(self.own2d, L, D)
+        self.neg = _kv_layers(self.neg2d, L, D) if has_neg else None
+
+    def layer(self, li, a, dcc, dq, delta, scale, drop):
+        """Cross-attention backward of layer li: a = the layer's activations, dcc the gradient of its context; writes dq and the layer's dK / dV."""
+        n, S, E, D = self.n, self.S, self.E, self.D
+        q, kv, cc, lse = a["q"], a["kv"], a["cc"], a["lse_c"]
+        fold = self.has_neg and not self.acc and not self.smallq
+        if fold and kv.stride(0) != 2 * D:
+            # one-launch triplet backward into a per-entry [3 n E, 2 D] buffer: dK / dV use the K / V strides, so this (rare) path reads a
+            # row-major copy of the layer's [own | neg] sets
+            kv = torch.as_strided(kv, (2 * n * E, 2 * D), (kv.stride(0), 1)).contiguous()
+        krs = kv.stride(0)
+        kw = dict(H=self.H, Sq=S, Sk=E, hd=D // self.H, scale=scale, mask=None, drop=drop,
+                  q_strides=(S * D, D), k_strides=(E * krs, krs), v_strides=(E * krs, krs), o_strides=(S * D, D))
+        if not self.has_neg or fold:
+            dkv = _empty((self.b * E, 2 * D), self.dt, dq.device) if fold else self.own[li]
+            ops.attn_bwd(q, kv, kv[:, D:], cc, dcc, lse, dq, dkv, dkv[:, D:], delta, B=self.b, kv_batch_mod=2 * n if fold else 0,
+                         dkv_accumulate=self.acc, **kw)
+            if fold:      # dK / dV per batch entry -> per K/V set: the triplet's first and third thirds read the same (own) set
+                ne = n * E
+                torch.add(dkv[:ne], dkv[2 * ne:], out=self.own[li])
+                self.neg[li].copy_(dkv[ne:2 * ne])
+        elif self.acc:
+            # three launches over the triplet: entries [0, n) and [2 n, 3 n) ADD their dK / dV to the session's own-set buffer (the captioning
+            # pass wrote it), entries [n, 2 n) write the hard negatives' buffer
+            ne, r1 = n * E, n * S
+            dko, dkn = self.own[li], self.neg[li]
+            assert dko.stride(0) == krs and dkn.stride(0) == krs
+            kvn = torch.as_strided(kv, kv.shape, kv.stride(), kv.storage_offset() + ne * krs)     # (kv = the own rows of the layer's [own | neg] sets)
+            for e0, kvs, dst, acc in ((0, kv, dko, True), (1, kvn, dkn, False), (2, kv, dko, True)):
+                rs = slice(e0 * r1, (e0 + 1) * r1)
+                ops.attn_bwd(q[rs], kvs, kvs[:, D:], cc[rs], dcc[rs], lse[e0 * n:(e0 + 1) * n], dq[rs], dst, dst[:, D:], delta, B=n,
+                             batch0=e0 * n, dkv_accumulate=acc, **kw)
+        else:
+            # two launches over the triplet: entries [0, 2 n) own exactly the [own | neg] K/V sets, entries [2 n, 3 n) read the own sets again
+            # and ADD their dK / dV (mico_attn_params.batch0 keeps the dropout counters of the one-launch forward)
+            dkv = self.pair[li]
+            assert dkv.stride(0) == krs
+            r2 = 2 * n * S
+            ops.attn_bwd(q[:r2], kv, kv[:, D:], cc[:r2], dcc[:r2], lse[:2 * n], dq[:r2], dkv, dkv[:, D:], delta, B=2 * n, **kw)
+            ops.attn_bwd(q[r2:], kv, kv[:, D:], cc[r2:], dcc[r2:], lse[2 * n:], dq[r2:], dkv, dkv[:, D:], delta, B=n, batch0=2 * n,
+                         dkv_accumulate=True, **kw)
+
+    def finish(self):
+        """(dkv_own, dkv_neg) for autograd - contiguous row blocks, 2-D like the memory; registers the own buffer with the session or closes it."""
+        if self.acc:          # the own set's gradient is in the buffer another pass handed to autograd
+            DkvSession.accumulated += 1
+            return None, self.neg2d
+        if self.sess is not None:
+            if self.sess.own is None and not self.sess.closed:
+                self.sess.own = self.own2d
+            else:
+                self.sess.closed = True      # a second buffer for the same set: the engine sums out of place from here on
+        return self.own2d, self.neg2d
+
+
+def _bert_layers(spec, P, x32, x16, *, qkv_bias, self_attn, cross_attn, hidden_drop, for_backward, sink):
+    """The encoder stack (bert.py:393-461, spec.L layers) on the embedding LayerNorm's output x32 fp32 [rows, D] / x16 (16-bit, [hi | lo] under
+    split_activations): returns the last layer's fp32 output.  P(name): parameter by name.  What differs between a training / scoring pass
+    (BertFn) and a step of the cached decode (BertDecodeCache) comes in from the caller:
+      qkv_bias(li)        the fused [3 D] bias of the self-attention projections;
+      self_attn(li, qkv)  -> (context [rows, D] 16-bit, dict of what its backward keeps - read only with a sink) from the fused qkv [rows, 3 D];
+      cross_attn(li, q)   likewise from the cross-attention queries q [rows, D] - it owns the K/V source; None: no cross-attention;
+      hidden_drop(site)   dropout of the three output projections (the `drop` of ops.gemm) or None;
+      for_backward        the LayerNorms emit mean / rstd and fc1 emits gelu'(h) next to gelu(h) (what BertFn.backward reads);
+      sink(a)             receives a layer's activations (the dict BertFn.backward pops) once the layer is done, or None: nothing is kept."""
+    rows = x16.shape[0]
+    dt, dev = x16.dtype, x16.device
+    D, I = spec.D, spec.I
+    split = runtime.split_activations()
+
+    def ln_out(u, pre):
+        o32 = _empty((rows, D), torch.float32, dev)
+        o16 = _empty((rows, 2 * D if split else D), dt, dev)
+        m_, r_ = (_empty((rows,), torch.float32, dev), _empty((rows,), torch.float32, dev)) if for_backward else (None, None)
+        ops.layernorm_fwd(u, P(pre + "LayerNorm.weight"), P(pre + "LayerNorm.bias"), spec.eps, out16=o16, out32=o32, mean=m_, rstd=r_,
+                          split16=split, dtype=dt)
+        return o32, o16, m_, r_
+
+    for li in range(spec.L):
+        p = f"encoder.layer.{li}."
+        sa = p + "attention.self."
+        x_in = x16
+        qkv = _empty((rows, 3 * D), dt, dev)
+        _fwd_gemm(x16, "bqkv", [P(sa + "query.weight"), P(sa + "key.weight"), P(sa + "value.weight")], qkv, bias=qkv_bias(li))
+        co, kept = self_attn(li, qkv)
+        u = _empty((rows, D), torch.float32, dev)
+        _fwd_gemm(co, "w1", [P(p + "attention.output.dense.weight")], u, bias=P(p + "attention.output.dense.bias"), resid=x32,
+                  drop=hidden_drop(li * 8 + SITE_SELF_OUT))
+        x32, x16, m1, r1 = ln_out(u, p + "attention.output.")
+        if cross_attn is not None:
+            ca = p + "crossattention.self."
+            x_a = x16
+            q = _empty((rows, D), dt, dev)
+            _fwd_gemm(x16, "w1", [P(ca + "query.weight")], q, bias=P(ca + "query.bias"))
+            cc, kept_c = cross_attn(li, q)
+            u2 = _empty((rows, D), torch.float32, dev)
+            _fwd_gemm(cc, "w1", [P(p + "crossattention.output.dense.weight")], u2, bias=P(p + "crossattention.output.dense.bias"), resid=x32,
+                      drop=hidden_drop(li * 8 + SITE_CROSS_OUT))
+            x32, x16, m2, r2 = ln_out(u2, p + "crossattention.output.")
+        x_b = x16
+        h = _empty((rows, I), dt, dev) if for_backward else None
+        act = _empty((rows, I), dt, dev)
+        _fwd_gemm(x16, "w1", [P(p + "intermediate.dense.weight")], act, bias=P(p + "intermediate.dense.bias"), aux_out=h,
+                  act=ops.ACT_GELU_SAVE_DERIV if for_backward else ops.ACT_GELU)
+        u3 = _empty((rows, D), torch.float32, dev)
+        _fwd_gemm(act, "w1", [P(p + "output.dense.weight")], u3, bias=P(p + "output.dense.bias"), resid=x32,
+                  drop=hidden_drop(li * 8 + SITE_FFN_OUT))
+        x32, x16, m3, r3 = ln_out(u3, p + "output.")
+        if sink is not None:
+            a = dict(kept, x16=x_in[:, :D], qkv=qkv, co=co, u=u, m1=m1, r1=r1, x16b=x_b[:, :D], h=h, act=act, u3=u3, m3=m3, r3=r3)
+            if cross_attn is not None:
+                a.update(kept_c, x16a=x_a[:, :D], q=q, cc=cc, u2=u2, m2=m2, r2=r2)
+            sink(a)
+    return x32
+
+
 class BertFn(torch.autograd.Function):
+    # forward's arguments in front of *params; backward finds its gradient slots and ctx.needs_input_grad entries by these names
+    ARGS = ("spec", "input_ids", "add_mask", "cond", "drop", "kv_own", "kv_neg", "kv_cache", "kv_index", "kv_sets")
+
     @staticmethod
-    def forward(ctx, spec, input_ids, add_mask, cond, drop, kv_own, kv_neg, *params):
-        """kv_own / kv_neg (CrossKVFn outputs, [L][n E, 2 D]) instead of cond: the cross-attention K/V memory is given; a batch of
+    def forward(ctx, spec, input_ids, add_mask, cond, drop, kv_own, kv_neg, kv_cache, kv_index, kv_sets, *params):
+        """kv_own / kv_neg (CrossKVFn outputs, 2-D [n E, L * 2 D]) instead of cond: the cross-attention K/V memory is given; a batch of
         n entries reads kv_own, one of 3 n entries is the ITM triplet [own | neg | own] and reads [kv_own | kv_neg] modulo 2 n.
-        drop: None (eval), (p_hidden, p_attention, seed) - train-mode dropout of bert.py:148,267,295,373 - or a dict
-        {"kv_cache": {...}} (inference only): the per-layer cross-attention K/V projections of `cond` are stored in / taken from
-        that dict, so a decode loop projects its (constant) condition tokens once instead of at every step; or a dict
-        {"kv_index": int32 [b], "kv_sets": n} (inference only, with the 2-D kv_own of cross_kv_memory holding n sets): batch entry i
+        drop: None (eval) or (p_hidden, p_attention, seed) - train-mode dropout of bert.py:148,267,295,373.
+        kv_cache (dict or None, inference only): the per-layer cross-attention K/V projections of `cond` are stored in / taken from
+        that dict, so a decode loop projects its (constant) condition tokens once instead of at every step.
+        kv_index (int32 [b] or None, inference only, with the kv_own of cross_kv_memory holding kv_sets sets): batch entry i
         attends to set kv_index[i] (mico_attn_params.kv_index) - retrieval re-ranking, where every candidate is projected once."""
         runtime.remember_precision(ctx)
-        kv_cache = kv_index = None
-        kv_sets = 0
-        if isinstance(drop, dict):
-            kv_cache, kv_index, kv_sets, drop = drop.get("kv_cache"), drop.get("kv_index"), int(drop.get("kv_sets", 0)), None
         dt = runtime.compute_dtype()
         ph, pa, dseed = drop if drop is not None else (0.0, 0.0, 0)
         hd_drop = (lambda site: (ph, dseed, site)) if ph > 0 else (lambda site: None)
@@ -1775,7 +1907,7 @@ class BertFn(torch.autograd.Function):
         P = lambda n: params[spec.idx[n]]
         dev = input_ids.device
         b, S = input_ids.shape
-        D, H, I = spec.D, spec.H, spec.I
+        D, H = spec.D, spec.H
         hd = D // H
         rows = b * S
         ids = input_ids.contiguous()
@@ -1792,101 +1924,71 @@ class BertFn(torch.autograd.Function):
         kv_mod = 0
         ctx.dkv_session = getattr(kv_own, "_mico_dkv", None) if kv_own is not None else None      # (DkvSession, attached by project_cross_kv)
         if kv_own is not None:
-            assert cond is None and kv_cache is None
+            # the shared memory is CrossKVFn's / cross_kv_memory's: [n E, L * 2 D] row-major, read per layer through its row stride
+            assert cond is None and kv_cache is None and kv_own.dim() == 2 and kv_own.is_contiguous() and kv_own.shape[1] == spec.L * 2 * D
             n_own = b if kv_neg is None else b // 3
             if kv_index is not None:
-                assert kv_neg is None and kv_own.dim() == 2 and kv_sets > 0 and kv_own.shape[0] % kv_sets == 0
+                assert kv_neg is None and kv_sets > 0 and kv_own.shape[0] % kv_sets == 0
                 n_own = kv_sets
-            kv_2d = kv_own.dim() == 2        # the interleaved memory: [n E, L * 2 D] row-major (CrossKVFn), read per layer through its row stride
-            if kv_2d:
-                assert kv_own.is_contiguous() and kv_own.shape[1] == spec.L * 2 * D
-                kv_own = _kv_layers(kv_own, spec.L, D)
-            E = kv_own.shape[1] // n_own
-            if kv_neg is not None:   # the triplet reads one [own | neg] buffer modulo 2 n: the two views must be adjacent per layer
-                if kv_2d:
-                    assert kv_neg.dim() == 2 and kv_neg.is_contiguous()
-                    kv_neg = _kv_layers(kv_neg, spec.L, D)
-                assert b == 3 * n_own and kv_neg.stride() == kv_own.stride() and \
-                    kv_neg.data_ptr() == kv_own.data_ptr() + n_own * E * kv_own.stride(1) * kv_own.element_size()
+            E = kv_own.shape[0] // n_own
+            if kv_neg is not None:   # the triplet reads one [own | neg] buffer modulo 2 n: the two row blocks must be adjacent
+                assert b == 3 * n_own and kv_neg.dim() == 2 and kv_neg.is_contiguous() and kv_neg.stride() == kv_own.stride() and \
+                    kv_neg.data_ptr() == kv_own.data_ptr() + n_own * E * kv_own.stride(0) * kv_own.element_size()
                 kv_mod = 2 * n_own
-        if cond is not None:
+            kv_layers = _kv_layers(kv_own, spec.L, D)
+
+            def layer_kv(li):
+                return kv_layers[li]      # with kv_mod: the first n E rows of the layer's [own | neg] buffer
+        elif cond is not None:
             E = cond.shape[1]
             cond16 = _empty((b * E, D), dt, dev)
             ops.cast_f32_to_16(cond.contiguous().view(b * E, D), cond16)
-        mask = add_mask.contiguous() if add_mask is not None else None
-        scale = 1.0 / math.sqrt(hd)
-        acts = []
 
-        split = runtime.split_activations()
-
-        def ln_out(u, pre):
-            o32 = _empty((rows, D), torch.float32, dev)
-            o16 = _empty((rows, 2 * D if split else D), dt, dev)
-            m_, r_ = _empty((rows,), torch.float32, dev), _empty((rows,), torch.float32, dev)
-            ops.layernorm_fwd(u, P(pre + "LayerNorm.weight"), P(pre + "LayerNorm.bias"), spec.eps, out16=o16, out32=o32, mean=m_, rstd=r_,
-                              split16=split, dtype=dt)
-            return o32, o16, m_, r_
-
-        for li in range(spec.L):
-            p = f"encoder.layer.{li}."
-            a = dict(x16=x16[:, :D])
-            sa = p + "attention.self."
-            bqkv = torch.cat((P(sa + "query.bias").detach(), P(sa + "key.bias").detach(), P(sa + "value.bias").detach()))
-            qkv = _empty((rows, 3 * D), dt, dev)
-            _fwd_gemm(x16, "bqkv", [P(sa + "query.weight"), P(sa + "key.weight"), P(sa + "value.weight")], qkv, bias=bqkv)
-            co = _empty((rows, D), dt, dev)
-            lse = _empty((b, H, S), torch.float32, dev)
-            st = dict(q_strides=(S * 3 * D, 3 * D), k_strides=(S * 3 * D, 3 * D), v_strides=(S * 3 * D, 3 * D), o_strides=(S * D, D))
-            ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], co, lse, B=b, H=H, Sq=S, Sk=S, hd=hd, scale=scale, mask=mask,
-                         drop=at_drop(li * 8 + SITE_SELF_P), **st)
-            wo = P(p + "attention.output.dense.weight")
-            u = _empty((rows, D), torch.float32, dev)
-            _fwd_gemm(co, "w1", [wo], u, bias=P(p + "attention.output.dense.bias"), resid=x32, drop=hd_drop(li * 8 + SITE_SELF_OUT))
-            x32, x16, m1, r1 = ln_out(u, p + "attention.output.")
-            a.update(qkv=qkv, co=co, lse=lse, u=u, m1=m1, r1=r1)
-            if cond16 is not None or kv_own is not None:
-                ca = p + "crossattention.self."
-                a["x16a"] = x16[:, :D]
-                q = _empty((rows, D), dt, dev)
-                _fwd_gemm(x16, "w1", [P(ca + "query.weight")], q, bias=P(ca + "query.bias"))
+            def layer_kv(li):      # projected per pass and layer; a kv_cache dict keeps the projections across the calls of a decode
                 kv = kv_cache.get(li) if kv_cache is not None else None
-                if kv_own is not None:
-                    kv = kv_own[li]      # with kv_mod: the first n E rows of the layer's [own | neg] buffer
-                elif kv is None or kv.shape[0] != b * E:
+                if kv is None or kv.shape[0] != b * E:
+                    ca = f"encoder.layer.{li}.crossattention.self."
                     bkv = torch.cat((P(ca + "key.bias").detach(), P(ca + "value.bias").detach()))
                     kv = _empty((b * E, 2 * D), dt, dev)
                     _fwd_gemm(cond16, "bkv", [P(ca + "key.weight"), P(ca + "value.weight")], kv, bias=bkv)
                     if kv_cache is not None:
                         kv_cache[li] = kv
-                cc = _empty((rows, D), dt, dev)
-                lse_c = _empty((b, H, S), torch.float32, dev)
-                krs = kv.stride(0)       # 2 D, or L * 2 D for a layer of the interleaved shared memory (CrossKVFn)
-                stc = dict(q_strides=(S * D, D), k_strides=(E * krs, krs), v_strides=(E * krs, krs), o_strides=(S * D, D))
-                ops.attn_fwd(q, kv, kv[:, D:], cc, lse_c, B=b, H=H, Sq=S, Sk=E, hd=hd, scale=scale, mask=None,
-                             drop=at_drop(li * 8 + SITE_CROSS_P), kv_batch_mod=kv_mod, kv_index=kv_index, **stc)
-                u2 = _empty((rows, D), torch.float32, dev)
-                _fwd_gemm(cc, "w1", [P(p + "crossattention.output.dense.weight")], u2,
-                          bias=P(p + "crossattention.output.dense.bias"), resid=x32, drop=hd_drop(li * 8 + SITE_CROSS_OUT))
-                x32, x16, m2, r2 = ln_out(u2, p + "crossattention.output.")
-                a.update(q=q, kv=kv, cc=cc, lse_c=lse_c, u2=u2, m2=m2, r2=r2)
-            a["x16b"] = x16[:, :D]
-            h = _empty((rows, I), dt, dev)
-            act = _empty((rows, I), dt, dev)
-            _fwd_gemm(x16, "w1", [P(p + "intermediate.dense.weight")], act, bias=P(p + "intermediate.dense.bias"),
-                      aux_out=h, act=ops.ACT_GELU_SAVE_DERIV)
-            u3 = _empty((rows, D), torch.float32, dev)
-            _fwd_gemm(act, "w1", [P(p + "output.dense.weight")], u3, bias=P(p + "output.dense.bias"), resid=x32,
-                      drop=hd_drop(li * 8 + SITE_FFN_OUT))
-            x32, x16, m3, r3 = ln_out(u3, p + "output.")
-            a.update(h=h, act=act, u3=u3, m3=m3, r3=r3)
-            if kv_index is None:      # (an indexed pass is inference by contract: a layer's activations are dropped as soon as the next one has read them)
-                acts.append(a)
+                return kv
+        mask = add_mask.contiguous() if add_mask is not None else None
+        scale = 1.0 / math.sqrt(hd)
+        st = dict(q_strides=(S * 3 * D, 3 * D), k_strides=(S * 3 * D, 3 * D), v_strides=(S * 3 * D, 3 * D), o_strides=(S * D, D))
+
+        def qkv_bias(li):
+            sa = f"encoder.layer.{li}.attention.self."
+            return torch.cat((P(sa + "query.bias").detach(), P(sa + "key.bias").detach(), P(sa + "value.bias").detach()))
+
+        def self_attn(li, qkv):
+            co = _empty((rows, D), dt, dev)
+            lse = _empty((b, H, S), torch.float32, dev)
+            ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], co, lse, B=b, H=H, Sq=S, Sk=S, hd=hd, scale=scale, mask=mask,
+                         drop=at_drop(li * 8 + SITE_SELF_P), **st)
+            return co, dict(lse=lse)
+
+        def cross_attn(li, q):
+            kv = layer_kv(li)
+            cc = _empty((rows, D), dt, dev)
+            lse_c = _empty((b, H, S), torch.float32, dev)
+            krs = kv.stride(0)       # 2 D, or L * 2 D for a layer of the shared memory
+            stc = dict(q_strides=(S * D, D), k_strides=(E * krs, krs), v_strides=(E * krs, krs), o_strides=(S * D, D))
+            ops.attn_fwd(q, kv, kv[:, D:], cc, lse_c, B=b, H=H, Sq=S, Sk=E, hd=hd, scale=scale, mask=None,
+                         drop=at_drop(li * 8 + SITE_CROSS_P), kv_batch_mod=kv_mod, kv_index=kv_index, **stc)
+            return cc, dict(kv=kv, lse_c=lse_c)
+
+        acts = []
+        # (an indexed pass is inference by contract: a layer's activations are dropped as soon as the next one has read them)
+        x32 = _bert_layers(spec, P, x32, x16, qkv_bias=qkv_bias, self_attn=self_attn,
+                           cross_attn=cross_attn if (cond16 is not None or kv_own is not None) else None, hidden_drop=hd_drop,
+                           for_backward=True, sink=acts.append if kv_index is None else None)
         ctx.spec, ctx.params, ctx.acts, ctx.dt = spec, params, acts, dt
         ctx.misc = (ids, emb, mean_e, rstd_e, cond16, mask, b, S, E)
         ctx.drop = drop
         ctx.cond_needs_grad = cond is not None and cond.requires_grad
-        ctx.kv_shared = (kv_own is not None, kv_neg is not None, kv_mod)
-        ctx.kv_2d = kv_own is not None and kv_2d
+        ctx.kv_shared = (kv_own is not None, kv_neg is not None)
         return x32.view(b, S, D)
 
     @staticmethod
@@ -1922,48 +2024,13 @@ class BertFn(torch.autograd.Function):
 
         g = dseq.contiguous().view(rows, D).float().clone()
         dcond = torch.zeros((b * E, D), dtype=torch.float32, device=dev) if cond16 is not None else None
-        shared, has_neg, kv_mod = ctx.kv_shared
-        n_own = (b // 3 if has_neg else b) if shared else 0
-        # gradients of the shared K/V memory, still in the 16-bit gradient scale (CrossKVFn.backward removes it)
-        # (ITM triplet: [own | neg] adjacent per layer - batch entries 0 .. 2 n of the backward write their dK / dV rows straight into the pair, the
-        # third third accumulates onto the own half in a second launch: no per-entry buffer, no add / copy passes)
-        kv_il = shared and ctx.kv_2d      # the memory is interleaved over the layers (a 2-D tensor to autograd): so are its gradients
-        dkv2d = None        # interleaved: the 2-D [rows, L * 2 D] buffer behind the per-layer views - what autograd gets back
-        # DkvSession: the passes that read one own set share ONE gradient buffer for it.  acc_own = the buffer an earlier backward of this pass
-        # wrote (this one adds to it in the attention kernel and returns None for kv_own).  Only when the engine wants kv_own's gradient in this
-        # pass at all - then CrossKVFn.backward runs after every reader and ends the session.
-        # (and only under an engine that can tell backward passes apart - the condition GradArena.session has: without it, a buffer per pass)
-        sess = ctx.dkv_session if (kv_il and runtime.CFG.dkv_inplace and ctx.needs_input_grad[5] and hasattr(torch._C, "_current_graph_task_id")) else None
-        acc_own = None
-        if sess is not None and sess.own is not None and not sess.closed:
-            if (ops.attn_bwd_smallq_ok(n_own, H, S, E, hd, at_drop(SITE_CROSS_P), batch0=2 * n_own if has_neg else 0)
-                    and tuple(sess.own.shape) == (n_own * E, spec.L * 2 * D) and sess.own.dtype == dt):
-                acc_own = sess.own
-            else:
-                sess.closed = True
-        dkv2d_neg = None
-        if acc_own is not None:
-            dkv_pair = None
-            dkv_own = _kv_layers(acc_own, spec.L, D)
-            dkv_neg = None
-            if has_neg:        # the triplet's hard negatives: only this pass reads them - a buffer of their own
-                dkv2d_neg = _empty((n_own * E, spec.L * 2 * D), dt, dev)
-                dkv_neg = _kv_layers(dkv2d_neg, spec.L, D)
-        elif has_neg:
-            if kv_il:
-                dkv2d = _empty((2 * n_own * E, spec.L * 2 * D), dt, dev)
-                dkv_pair = _kv_layers(dkv2d, spec.L, D)
-            else:
-                dkv_pair = _empty((spec.L, 2 * n_own * E, 2 * D), dt, dev)
-            dkv_own, dkv_neg = dkv_pair[:, :n_own * E], dkv_pair[:, n_own * E:]
-        else:
-            dkv_pair = None
-            dkv_neg = None
-            if shared and kv_il:
-                dkv2d = _empty((n_own * E, spec.L * 2 * D), dt, dev)
-                dkv_own = _kv_layers(dkv2d, spec.L, D)
-            else:
-                dkv_own = _empty((spec.L, n_own * E, 2 * D), dt, dev) if shared else None
+        shared, has_neg = ctx.kv_shared
+        route = None
+        if shared:
+            # (the session only when the engine wants kv_own's gradient in this pass at all - then CrossKVFn.backward runs after every reader and
+            # ends it)
+            wanted = ctx.needs_input_grad[BertFn.ARGS.index("kv_own")]
+            route = _SharedDkv(ctx.dkv_session if wanted else None, spec, b, S, E, has_neg, at_drop(SITE_CROSS_P), dt, dev)
 
         def ln_bwd(gin, u, m_, r_, pre, site):
             """d(LN input) fp32 (in place into gin: the residual branch's gradient) and its scaled 16-bit copy for the dense
@@ -1996,62 +2063,26 @@ class BertFn(torch.autograd.Function):
                 ops.gemm(d16, _fused_w("w1", [P(p + "crossattention.output.dense.weight")]), dcc, tb=True, M=rows, N=D, K=D)
                 dq = _empty((rows, D), dt, dev)
                 delta = _empty((b, H, S), torch.float32, dev)
-                kv = a["kv"]
-                two_launch = shared and has_neg and ops.attn_bwd_smallq_ok(n_own, H, S, E, hd, at_drop(li * 8 + SITE_CROSS_P), batch0=2 * n_own)
-                if shared and has_neg and not two_launch and kv.stride(0) != 2 * D:
-                    # one-launch triplet backward into a per-entry [3 n E, 2 D] buffer: dK / dV use the K / V strides, so this (rare) path reads a
-                    # row-major copy of the layer's [own | neg] sets
-                    kv = torch.as_strided(kv, (2 * n_own * E, 2 * D), (kv.stride(0), 1)).contiguous()
-                krs = kv.stride(0)
-                stc = dict(q_strides=(S * D, D), k_strides=(E * krs, krs), v_strides=(E * krs, krs), o_strides=(S * D, D))
-                if two_launch and acc_own is None:
-                    assert dkv_pair[li].stride(0) == krs
-                if acc_own is not None and has_neg:
-                    # three launches over the triplet: entries [0, n) and [2 n, 3 n) ADD their dK / dV to the session's own-set buffer (the captioning
-                    # pass wrote it), entries [n, 2 n) write the hard negatives' buffer
-                    ne, r1 = n_own * E, n_own * S
-                    dko, dkn = dkv_own[li], dkv_neg[li]
-                    assert dko.stride(0) == krs and dkn.stride(0) == krs
-                    kvn = torch.as_strided(kv, kv.shape, kv.stride(), kv.storage_offset() + ne * krs)     # (kv = the own rows of the layer's [own | neg] sets)
-                    for e0, kvs, dst, acc in ((0, kv, dko, True), (1, kvn, dkn, False), (2, kv, dko, True)):
-                        rs = slice(e0 * r1, (e0 + 1) * r1)
-                        ops.attn_bwd(a["q"][rs], kvs, kvs[:, D:], a["cc"][rs], dcc[rs], a["lse_c"][e0 * n_own:(e0 + 1) * n_own], dq[rs], dst, dst[:, D:],
-                                     delta, B=n_own, H=H, Sq=S, Sk=E, hd=hd, scale=scale, mask=None, drop=at_drop(li * 8 + SITE_CROSS_P),
-                                     batch0=e0 * n_own, dkv_accumulate=acc, **stc)
-                    dkv = None
-                    split_done = True
-                elif shared and has_neg and ops.attn_bwd_smallq_ok(n_own, H, S, E, hd, at_drop(li * 8 + SITE_CROSS_P), batch0=2 * n_own):
-                    # two launches over the triplet: entries [0, 2 n) own exactly the [own | neg] K/V sets, entries [2 n, 3 n) read the own sets again
-                    # and ADD their dK / dV (mico_attn_params.batch0 keeps the dropout counters of the one-launch forward)
-                    dkv = dkv_pair[li]
-                    r2 = 2 * n_own * S
-                    ops.attn_bwd(a["q"][:r2], kv, kv[:, D:], a["cc"][:r2], dcc[:r2], a["lse_c"][:2 * n_own], dq[:r2], dkv, dkv[:, D:], delta,
-                                 B=2 * n_own, H=H, Sq=S, Sk=E, hd=hd, scale=scale, mask=None, drop=at_drop(li * 8 + SITE_CROSS_P), **stc)
-                    ops.attn_bwd(a["q"][r2:], kv, kv[:, D:], a["cc"][r2:], dcc[r2:], a["lse_c"][2 * n_own:], dq[r2:], dkv, dkv[:, D:], delta,
-                                 B=n_own, H=H, Sq=S, Sk=E, hd=hd, scale=scale, mask=None, drop=at_drop(li * 8 + SITE_CROSS_P), batch0=2 * n_own,
-                                 dkv_accumulate=True, **stc)
-                    split_done = True
+                drop_c = at_drop(li * 8 + SITE_CROSS_P)
+                if shared:
+                    route.layer(li, a, dcc, dq, delta, scale, drop_c)
                 else:
-                    split_done = False
-                    dkv = dkv_own[li] if (shared and not has_neg) else _empty((b * E, 2 * D), dt, dev)
+                    kv = a["kv"]
+                    stc = dict(q_strides=(S * D, D), k_strides=(E * 2 * D, 2 * D), v_strides=(E * 2 * D, 2 * D), o_strides=(S * D, D))
+                    dkv = _empty((b * E, 2 * D), dt, dev)
                     ops.attn_bwd(a["q"], kv, kv[:, D:], a["cc"], dcc, a["lse_c"], dq, dkv, dkv[:, D:], delta, B=b, H=H, Sq=S, Sk=E,
-                                 hd=hd, scale=scale, mask=None, drop=at_drop(li * 8 + SITE_CROSS_P), kv_batch_mod=kv_mod,
-                                 dkv_accumulate=acc_own is not None, **stc)
+                                 hd=hd, scale=scale, mask=None, drop=drop_c, **stc)
                 linear_wgrad(dq, a["x16a"], G(ca + "query.weight"), inv_s)
                 ops.colsum(dq, G(ca + "query.bias"), scale=inv_s, accumulate=True)
-                if shared:   # dK/dV per batch entry -> per K/V set: the triplet's first and third thirds read the same (own) set
-                    ne = n_own * E
-                    if has_neg and not split_done:
-                        torch.add(dkv[:ne], dkv[2 * ne:], out=dkv_own[li])
-                        dkv_neg[li].copy_(dkv[ne:2 * ne])
-                else:
+                if not shared:
                     linear_wgrad(dkv, cond16, GF([ca + "key.weight", ca + "value.weight"], (2 * D, D)), inv_s)
                     ops.colsum(dkv, GF([ca + "key.bias", ca + "value.bias"], (2 * D,)), scale=inv_s, accumulate=True)
-                if ctx.cond_needs_grad:
-                    wkv = _fused_w("bkv", [P(ca + "key.weight"), P(ca + "value.weight")])
-                    ops.gemm(dkv, wkv, dcond, tb=True, M=b * E, N=D, K=2 * D, alpha=inv_s, accumulate=True)
+                    if ctx.cond_needs_grad:
+                        wkv = _fused_w("bkv", [P(ca + "key.weight"), P(ca + "value.weight")])
+                        ops.gemm(dkv, wkv, dcond, tb=True, M=b * E, N=D, K=2 * D, alpha=inv_s, accumulate=True)
+                    del dkv
                 ops.gemm(dq, _fused_w("w1", [P(ca + "query.weight")]), g, tb=True, M=rows, N=D, K=D, alpha=inv_s, resid=g)
-                del dq, dkv, dcc
+                del dq, dcc
             # ---- self attention ----
             sa = p + "attention.self."
             d16 = ln_bwd(g, a["u"], a["m1"], a["r1"], p + "attention.output.", li * 8 + SITE_SELF_OUT)
@@ -2078,18 +2109,12 @@ class BertFn(torch.autograd.Function):
         dtype0 = torch.zeros(D, dtype=torch.float32, device=dev)
         ops.embed_scatter_add(ids, g, G("embeddings.word_embeddings.weight"), G("embeddings.position_embeddings.weight"), dtype0, S)
         G("embeddings.token_type_embeddings.weight")[0].add_(dtype0)
-        dc = dcond.view(b, E, D) if (dcond is not None and ctx.cond_needs_grad) else None
-        if dkv2d is not None:      # contiguous row blocks [own | neg] of the one buffer
-            dkv_own, dkv_neg = (dkv2d[:n_own * E], dkv2d[n_own * E:]) if has_neg else (dkv2d, None)
-        if acc_own is not None:    # the own set's gradient is in the buffer another pass handed to autograd
-            dkv_own, dkv_neg = None, dkv2d_neg
-            DkvSession.accumulated += 1
-        elif sess is not None:
-            if sess.own is None and not sess.closed and dkv2d is not None:
-                sess.own = dkv_own
-            else:
-                sess.closed = True      # a second buffer for the same set: the engine sums out of place from here on
-        return (None, None, None, dc, None, dkv_own, dkv_neg) + grads.result()
+        lead = dict.fromkeys(BertFn.ARGS)
+        if dcond is not None and ctx.cond_needs_grad:
+            lead["cond"] = dcond.view(b, E, D)
+        if shared:
+            lead["kv_own"], lead["kv_neg"] = route.finish()
+        return tuple(lead.values()) + grads.result()
 
 
 # ======================================================================================================================
@@ -2100,37 +2125,47 @@ class BertFn(torch.autograd.Function):
 VOCAB_PAD = 64
 
 
+def _lm_head_fwd(seq, wt, bt, g, beta, wdec, bdec, *, for_backward, logits_dtype):
+    """dense + GELU -> LayerNorm -> decoder GEMM over the vocabulary padded to VOCAB_PAD (bert.py:575-609) on every row of seq [..., D].
+    for_backward: the pre-activation and the LayerNorm's mean / rstd are kept (else None).  logits_dtype: None = the compute dtype.
+    Returns (logits [rows, Vp], x16, pre, act, hl, mean, rstd)."""
+    dt = runtime.compute_dtype()
+    dev = seq.device
+    D = seq.shape[-1]
+    x = seq.reshape(-1, D).contiguous().float()
+    rows = x.shape[0]
+    V = wdec.shape[0]
+    Vp = (V + VOCAB_PAD - 1) // VOCAB_PAD * VOCAB_PAD
+    x16 = _empty((rows, D), dt, dev)
+    ops.cast_f32_to_16(x, x16)
+    pre = _empty((rows, D), dt, dev) if for_backward else None
+    act = _empty((rows, D), dt, dev)
+    _fwd_gemm(x16, "w1", [wt], act, bias=bt.detach(), aux_out=pre, act=ops.ACT_GELU)
+    hl = _empty((rows, D), dt, dev)
+    mean, rstd = (_empty((rows,), torch.float32, dev), _empty((rows,), torch.float32, dev)) if for_backward else (None, None)
+    ops.layernorm_fwd(act, g.detach(), beta.detach(), 1e-12, out16=hl, mean=mean, rstd=rstd, dtype=dt)
+    wd16, ksd = runtime.gemm_weight([wdec], "wdec", n_pad=Vp)
+    bpad = torch.zeros(Vp, dtype=torch.float32, device=dev)
+    bpad[:V] = bdec.detach()
+    logits = _empty((rows, Vp), logits_dtype or dt, dev)
+    ops.gemm(hl, wd16, logits, bias=bpad, ksegs=ksd)
+    return logits, x16, pre, act, hl, mean, rstd
+
+
 class LMHeadLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, seq, labels, wt, bt, g, beta, wdec, bdec):
         runtime.remember_precision(ctx)
-        dt = runtime.compute_dtype()
-        dev = seq.device
-        D = seq.shape[-1]
-        x = seq.reshape(-1, D).contiguous().float()
         lab = labels.reshape(-1).contiguous()
-        rows = x.shape[0]
+        logits, x16, pre, act, hl, mean, rstd = _lm_head_fwd(seq, wt, bt, g, beta, wdec, bdec, for_backward=True, logits_dtype=None)
+        rows, Vp = logits.shape
         V = wdec.shape[0]
-        Vp = (V + VOCAB_PAD - 1) // VOCAB_PAD * VOCAB_PAD
-        x16 = _empty((rows, D), dt, dev)
-        ops.cast_f32_to_16(x, x16)
-        pre = _empty((rows, D), dt, dev)
-        act = _empty((rows, D), dt, dev)
-        _fwd_gemm(x16, "w1", [wt], act, bias=bt.detach(), aux_out=pre, act=ops.ACT_GELU)
-        hl = _empty((rows, D), dt, dev)
-        mean, rstd = _empty((rows,), torch.float32, dev), _empty((rows,), torch.float32, dev)
-        ops.layernorm_fwd(act, g.detach(), beta.detach(), 1e-12, out16=hl, mean=mean, rstd=rstd, dtype=dt)
-        wd16, ksd = runtime.gemm_weight([wdec], "wdec", n_pad=Vp)
-        bpad = torch.zeros(Vp, dtype=torch.float32, device=dev)
-        bpad[:V] = bdec.detach()
-        logits = _empty((rows, Vp), dt, dev)
-        ops.gemm(hl, wd16, logits, bias=bpad, ksegs=ksd)
-        row_loss = _empty((rows,), torch.float32, dev)
+        row_loss = _empty((rows,), torch.float32, seq.device)
         ops.ce_fwd_bwd(logits, lab, cols=V, row_loss=row_loss)
         n_valid = (lab != -100).sum().clamp_min(1).float()
         loss = row_loss.sum() / n_valid
         ctx.save_for_backward(x16, pre, act, hl, mean, rstd, logits, lab, n_valid, wt, g, wdec)
-        ctx.meta = (dt, V, Vp, seq.shape)
+        ctx.meta = (logits.dtype, V, Vp, seq.shape)
         return loss
 
     @staticmethod
@@ -2177,24 +2212,8 @@ class LMLogitsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, seq, wt, bt, g, beta, wdec, bdec):
-        dt = runtime.compute_dtype()
-        dev = seq.device
-        D = seq.shape[-1]
-        x = seq.reshape(-1, D).contiguous().float()
-        rows = x.shape[0]
         V = wdec.shape[0]
-        Vp = (V + VOCAB_PAD - 1) // VOCAB_PAD * VOCAB_PAD
-        x16 = _empty((rows, D), dt, dev)
-        ops.cast_f32_to_16(x, x16)
-        act = _empty((rows, D), dt, dev)
-        _fwd_gemm(x16, "w1", [wt], act, bias=bt.detach(), act=ops.ACT_GELU)
-        hl = _empty((rows, D), dt, dev)
-        ops.layernorm_fwd(act, g.detach(), beta.detach(), 1e-12, out16=hl, dtype=dt)
-        wd16, ksd = runtime.gemm_weight([wdec], "wdec", n_pad=Vp)
-        bpad = torch.zeros(Vp, dtype=torch.float32, device=dev)
-        bpad[:V] = bdec.detach()
-        logits = _empty((rows, Vp), torch.float32, dev)
-        ops.gemm(hl, wd16, logits, bias=bpad, ksegs=ksd)
+        logits = _lm_head_fwd(seq, wt, bt, g, beta, wdec, bdec, for_backward=False, logits_dtype=torch.float32)[0]
         ctx.mark_non_differentiable(logits)
         return logits[:, :V].reshape(*seq.shape[:-1], V)
 
@@ -2250,13 +2269,8 @@ class BertDecodeCache:
             self.E = E = cond.shape[1]
             cond16 = _empty((self.sets * E, D), dt, dev)
             ops.cast_f32_to_16(cond.float().contiguous().view(self.sets * E, D), cond16)
-            kvp = []
-            for li in range(L):
-                ca = f"encoder.layer.{li}.crossattention.self."
-                kvp += [params[spec.idx[ca + n]] for n in ("key.weight", "key.bias", "value.weight", "value.bias")]
             self.kvx = _empty((self.sets * E, L * 2 * D), dt, dev)
-            _fwd_gemm(cond16, "bkv_all", _kv_all_weights(kvp, L), self.kvx,
-                      bias=torch.cat([kvp[4 * li + j].detach() for li in range(L) for j in (1, 3)]))
+            _project_kv_all(cond16, cross_kv_params(spec, params), L, self.kvx)
 
     def reorder(self, parent):
         """Beam search: row r continues the prefix of row parent[r] (int64 [rows]) - the cached positions that stay, [0, filled - 1),
@@ -2291,7 +2305,7 @@ class BertDecodeCache:
         if BertDecodeCache.passes is not None:
             BertDecodeCache.passes.append((rows, n))
         dev = ids.device
-        D, H, I, L = spec.D, spec.H, spec.I, spec.L
+        D, H = spec.D, spec.H
         hd = D // H
         N = rows * n
         scale = 1.0 / math.sqrt(hd)
@@ -2300,46 +2314,31 @@ class BertDecodeCache:
         ops.bert_embed_fwd(ids.contiguous(), P("embeddings.word_embeddings.weight"), P("embeddings.position_embeddings.weight")[pos0:],
                            P("embeddings.token_type_embeddings.weight")[0].contiguous(), emb, n)
         split = runtime.split_activations()
-
-        def ln_out(u, pre):
-            o32, o16 = _empty((N, D), torch.float32, dev), _empty((N, 2 * D if split else D), dt, dev)
-            ops.layernorm_fwd(u, P(pre + "LayerNorm.weight"), P(pre + "LayerNorm.bias"), spec.eps, out16=o16, out32=o32, split16=split, dtype=dt)
-            return o32, o16
-
-        x32, x16 = ln_out(emb, "embeddings.")
+        x32, x16 = _empty((N, D), torch.float32, dev), _empty((N, 2 * D if split else D), dt, dev)
+        ops.layernorm_fwd(emb, P("embeddings.LayerNorm.weight"), P("embeddings.LayerNorm.bias"), spec.eps, out16=x16, out32=x32, split16=split,
+                          dtype=dt)
         sk = pos0 + n
-        for li in range(L):
-            p = f"encoder.layer.{li}."
-            sa = p + "attention.self."
-            qkv = _empty((N, 3 * D), dt, dev)
-            _fwd_gemm(x16, "bqkv", [P(sa + "query.weight"), P(sa + "key.weight"), P(sa + "value.weight")], qkv, bias=self.bqkv[li])
+
+        def self_attn(li, qkv):
             kv = self.kv[li]
             ops.decode_kv_append(qkv[:, D:], kv, rows=rows, n_new=n, pos0=pos0)
             co = _empty((N, D), dt, dev)
-            # self-attention: every row is a key set of its own (its cache), read by its n new positions under their mask rows
+            # every row is a key set of its own (its cache), read by its n new positions under their mask rows
             ops.attn_decode(qkv, kv, kv[:, :, D:], co, sets=rows, rows_per_set=1, q_per_row=n, H=H, Sk=sk, hd=hd, scale=scale, q_rs=3 * D,
                             kv_strides=(kv.stride(0), kv.stride(1)), o_rs=D, mask=self.mask[:, pos0:],
                             mask_strides=(self.mask.stride(0), self.mask.stride(1)))
-            u = _empty((N, D), torch.float32, dev)
-            _fwd_gemm(co, "w1", [P(p + "attention.output.dense.weight")], u, bias=P(p + "attention.output.dense.bias"), resid=x32)
-            x32, x16 = ln_out(u, p + "attention.output.")
-            if self.kvx is not None:
-                ca = p + "crossattention.self."
-                q = _empty((N, D), dt, dev)
-                _fwd_gemm(x16, "w1", [P(ca + "query.weight")], q, bias=P(ca + "query.bias"))
-                cc = _empty((N, D), dt, dev)
-                kvl = self.kvx[:, li * 2 * D:]
-                # cross-attention: the rows_per_set x n queries of a condition set share its keys
-                ops.attn_decode(q, kvl, kvl[:, D:], cc, sets=self.sets, rows_per_set=self.R, q_per_row=n, H=H, Sk=self.E, hd=hd, scale=scale,
-                                q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
-                u2 = _empty((N, D), torch.float32, dev)
-                _fwd_gemm(cc, "w1", [P(p + "crossattention.output.dense.weight")], u2, bias=P(p + "crossattention.output.dense.bias"), resid=x32)
-                x32, x16 = ln_out(u2, p + "crossattention.output.")
-            act = _empty((N, I), dt, dev)
-            _fwd_gemm(x16, "w1", [P(p + "intermediate.dense.weight")], act, bias=P(p + "intermediate.dense.bias"), act=ops.ACT_GELU)
-            u3 = _empty((N, D), torch.float32, dev)
-            _fwd_gemm(act, "w1", [P(p + "output.dense.weight")], u3, bias=P(p + "output.dense.bias"), resid=x32)
-            x32, x16 = ln_out(u3, p + "output.")
+            return co, None
+
+        def cross_attn(li, q):
+            cc = _empty((N, D), dt, dev)
+            kvl = self.kvx[:, li * 2 * D:]
+            # the rows_per_set x n queries of a condition set share its keys
+            ops.attn_decode(q, kvl, kvl[:, D:], cc, sets=self.sets, rows_per_set=self.R, q_per_row=n, H=H, Sk=self.E, hd=hd, scale=scale,
+                            q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
+            return cc, None
+
+        x32 = _bert_layers(spec, P, x32, x16, qkv_bias=self.bqkv.__getitem__, self_attn=self_attn,
+                           cross_attn=cross_attn if self.kvx is not None else None, hidden_drop=lambda site: None, for_backward=False, sink=None)
         self.filled = sk
         return LMLogitsFn.apply(x32.view(rows, n, D)[:, n - 1:, :], *self.head)[:, 0, :]
 

@@ -110,10 +110,7 @@ class BertModel(nn.Module):
         Without grad (evaluation): no autograd node and no gradient session; cond_own may be 16-bit (the compute dtype) and kv_own is the
         interleaved [b E, L 2 D] memory that forward(cross_kv=kv_own, kv_index=...) reads by index."""
         spec, params = self._bert_spec()
-        kvp = []
-        for li in range(spec.L):
-            ca = f"encoder.layer.{li}.crossattention.self."
-            kvp += [params[spec.idx[ca + n]] for n in ("key.weight", "key.bias", "value.weight", "value.bias")]
+        kvp = Fn.cross_kv_params(spec, params)
         if not torch.is_grad_enabled() and cond_neg is None:
             return Fn.cross_kv_memory(spec, cond_own, kvp), None
         session = Fn.DkvSession()
@@ -146,7 +143,7 @@ class BertModel(nn.Module):
         if kv_cache is not None:
             if torch.is_grad_enabled() and any(p.requires_grad for p in params):
                 raise RuntimeError("kv_cache is an inference feature: call under torch.no_grad()")
-            drop = {"kv_cache": kv_cache}
+            drop = None      # (an inference pass: no dropout)
         kv_own, kv_neg = (None, None)
         if cross_kv is not None:
             if encoder_hidden_states is not None or kv_cache is not None:
@@ -163,13 +160,13 @@ class BertModel(nn.Module):
                     raise ValueError("kv_index needs cross_kv as [sets, E, L 2 D], or as [sets E, L 2 D] with kv_sets=sets")
                 if kv_index.dtype != torch.int32 or kv_index.shape != (input_ids.shape[0],):
                     raise ValueError("kv_index is an int32 [batch] tensor")
-                drop = {"kv_index": kv_index.contiguous(), "kv_sets": int(kv_sets)}
+                drop, kv_index = None, kv_index.contiguous()
             if kv_neg is not None and input_ids.shape[0] % 3:
                 raise ValueError("cross_kv with hard negatives expects the ITM triplet batch [own | negative | own]")
         elif kv_index is not None:
             raise ValueError("kv_index needs cross_kv")
         seq = Fn.BertFn.apply(spec, input_ids, extended_attention_mask(attention_mask), encoder_hidden_states, drop, kv_own, kv_neg,
-                              *params)
+                              kv_cache, kv_index, int(kv_sets or 0), *params)
         return _Out(last_hidden_state=seq)
 
 

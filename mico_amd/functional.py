@@ -318,12 +318,12 @@ def _gemm_dx(dy16, plist, tag, out, k_pad=None, n_pad=None, ln=True, **epi):
     return ops.gemm(dy16, runtime.gemm_weight(plist, tag, ln_fed=ln)[0], out, tb=True, M=dy16.shape[0], N=k_in, K=n_out, **epi)
 
 
-def _aux_buf(M, N, K, dt, dev):
+def _aux_buf(M, N, K, dt, dev, tiled_ok=True):
     """(buffer, tiled) for an MLP's gelu'(pre-activation) tensor between its forward GEMM and its backward (ops.aux_buffer).  Row-major where one
     of the two launches leaves the 16-bit persistent kernel: fp8 mode (the dX launch is an MX-fp8 one), the parity configuration (activation
     [hi | lo]: three k-segments; the weights-split head blocks of the timed precision - x W_hi + x W_lo on the wrapped A stream - stay tiled).
     The same buffer carries the PRE-ACTIVATION where the block keeps that instead (_mlp_keeps_pre)."""
-    return ops.aux_buffer(M, N, K, dt, dev, tiled_ok=not (runtime.fp8_enabled() or runtime.split_activations()))
+    return ops.aux_buffer(M, N, K, dt, dev, tiled_ok=tiled_ok and not (runtime.fp8_enabled() or runtime.split_activations()))
 
 
 def _mlp_keeps_pre():
@@ -521,18 +521,157 @@ class PatchKeep:
         return out
 
 
-_TAIL_EXP = None   # experiment hook (tools/precision_probe.py --tail)
+# What one _tower_forward / _tower_backward call knows about itself - the parameter (and, in a backward, gradient) lookups, the geometry of
+# the pass and its attention strides - derived once, by the same code for both directions.
+# Forward: plan (DropPlan | None), diet (TowerDiet), save.  Backward (grads given): G, the gradient scale S / inv_s and the hand-over switch.
+class _TowerPass:
+    def __init__(self, spec, params, Bf, dt, keep, plan=None, diet=None, save=False, grads=None):
+        self.spec, self.arch, self.keep = spec, spec.arch, keep
+        self.P = lambda n: params[spec.idx[n]]
+        self.dt, self.dev, self.Bf = dt, params[0].device, Bf
+        self.N = N = spec.N if keep is None else keep.N       # tokens per frame of THIS pass (patch dropout: CLS + the kept patches)
+        self.D = D = spec.D
+        self.H, self.hd, self.Hd = spec.H, spec.hd, spec.hidden
+        # (SwiGLU) the hidden width of the buffers, == Hd unless it needs padding (see TowerSpec), and what the GEMMs are told then
+        self.Hp, self.npad = spec.hidden_pad, (spec.hidden_pad if spec.hidden_pad != spec.hidden else None)
+        self.strides = dict(q_strides=(N * 3 * D, 3 * D), k_strides=(N * 3 * D, 3 * D), v_strides=(N * 3 * D, 3 * D), o_strides=(N * D, D))
+        self.plan, self.diet, self.save = plan, diet, save
+        self.xh16 = diet is not None and diet.xh16 and save      # the LayerNorm input rows are kept as fp16 normalised rows (TowerDiet.xh16)
+        if grads is not None:
+            self.G = lambda n: grads.get(spec.idx[n])
+            self.S, self.fuse = runtime.grad_scale(), runtime.CFG.fuse_grad_handover
+            self.inv_s = 1.0 / self.S
+
+    # ---- forward ----
+    def branch_io(self, i, which):
+        """-> (kept frames, frame list | None, scale vector | None, DropPlan.transition | None) of branch `which` of block i"""
+        p = self.plan
+        return p.branch(i, which) + (p.transition(i, which),) if p is not None else (self.Bf, None, None, None)
+
+    # Where a branch's output projection writes the residual stream.  Every frame kept: out of place, the input buffer itself is the saved
+    # LayerNorm input; otherwise the epilogue scatters the kept frames onto the stream in place and the LayerNorm's compact copy is what is
+    # saved (with the fp16 normalised rows kept instead, nothing reads the stream again: in place either way).
+    def stream_out(self, x, fmap):
+        return _empty((self.Bf * self.N, self.D), torch.float32, self.dev) if (fmap is None and self.save and not self.xh16) else x
+
+    # ---- backward: the 16-bit gradient operand of a branch and its hand-over from the LayerNorm backward of the branch before it ----
+    def take_g16(self, g, pre, rows, fmap, sc):
+        """The branch's 16-bit gradient operand [rows, D] = S * sc[frame] * g over its kept frames: handed over by the previous LayerNorm
+        backward (only the frames that branch did not keep are still gathered), or gathered whole."""
+        N, S = self.N, self.S
+        if pre is not None:
+            g16, dframes, ddst = pre
+            if dframes is not None and dframes.numel() > 0:
+                ops.gather_rows_cast(g, g16, row_scale=sc, rows_per_scale=N, scale=S, frame_map=dframes, rows_per_frame=N, dst_map=ddst)
+            return g16
+        g16 = _empty((rows, self.D), self.dt, self.dev)
+        ops.gather_rows_cast(g, g16, row_scale=sc, rows_per_scale=N, scale=S, frame_map=fmap, rows_per_frame=N)
+        return g16
+
+    def handover(self, tr, nb, nsc, had_plan):
+        """LayerNorm-backward arguments that make it write the next branch's operand (nb kept frames, per-frame scale nsc), and the `pre`
+        tuple for take_g16().  tr: DropPlan.transition of the current branch (None without a plan: both branches keep every frame)."""
+        if not self.fuse or nb <= 0 or (had_plan and tr is None):
+            return {}, None
+        g16n = _empty((nb * self.N, self.D), self.dt, self.dev)
+        if tr is None:
+            return dict(dx16=g16n, scale16=self.S), (g16n, None, None)
+        return dict(dx16=g16n, scale16=self.S, dx16_dst=tr[0], dx16_frame_scale=nsc), (g16n, tr[1], tr[2])
+
+
+# ---- launches that more than one block kind or direction issues ----
+def _qkv_bias(P, b):
+    """fused qkv bias (q_bias | 0 | v_bias): the key projection has none (eva_vit_model.py:318-321)"""
+    qb, vb = P(b + "attn.q_bias").detach(), P(b + "attn.v_bias").detach()
+    return torch.cat((qb, torch.zeros_like(qb), vb))
+
+
+def _qkv_bias_grad(G, b, dbias, D):
+    """the fused bias gradient [3 D] (filled by the qkv weight-gradient launch) -> q_bias, v_bias"""
+    G(b + "attn.q_bias").add_(dbias[:D])
+    G(b + "attn.v_bias").add_(dbias[2 * D:])
+
+
+# Rotate the q and k thirds of t [B N, 3 D] in place (inverse: their gradients).  Under patch dropout each kept token rotates with its
+# own patch's table row (rope.py:120-136).
+def _rope_qk(tp, t, B, fmap, inverse=False):
+    if tp.spec.rope is None:
+        return
+    N, D, (cos_t, sin_t) = tp.N, tp.D, tp.spec.rope
+    for part in (t, t[:, D:]):
+        if tp.keep is not None:
+            ops.rope_keep(part, N * 3 * D, 3 * D, B, N, tp.H, tp.hd, cos_t, sin_t, tp.keep.dev, frame_map=fmap, inverse=inverse)
+        else:
+            ops.rope(part, N * 3 * D, 3 * D, B, N, tp.H, tp.hd, cos_t, sin_t, inverse=inverse)
+
+
+def _self_attn_forward(tp, qkv, B):
+    """-> (attention output [B N, D], log-sum-exp [B, H, N]) of B frames' fused qkv rows"""
+    N, D, H, hd = tp.N, tp.D, tp.H, tp.hd
+    ao, lse = _empty((B * N, D), tp.dt, tp.dev), _empty((B, H, N), torch.float32, tp.dev)
+    ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], ao, lse, B=B, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **tp.strides)
+    return ao, lse
+
+
+def _self_attn_backward(tp, a, dao, B):
+    """-> dqkv [B N, 3 D] from the saved qkv / ao / lse of `a` and the gradient of the attention output"""
+    N, D, H, hd = tp.N, tp.D, tp.H, tp.hd
+    qkv = a["qkv"]
+    dqkv, delta = _empty((B * N, 3 * D), tp.dt, tp.dev), _empty((B, H, N), torch.float32, tp.dev)
+    ops.attn_bwd(qkv, qkv[:, D:], qkv[:, 2 * D:], a["ao"], dao, a["lse"], dqkv, dqkv[:, D:], dqkv[:, 2 * D:], delta,
+                 B=B, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **tp.strides)
+    return dqkv
+
+
+# act = GELU(fc1 x16) [rows, hidden] and what the backward finds next to it.  stash: "pre" = a copy of the pre-activation leaving from the
+# registers (2 hidden bytes per token kept, _mlp_keeps_pre), "pair" = GELU' (the backward multiplies by it), None = nothing: half the output
+# bytes of the launch.  ln: x16 comes from a LayerNorm;  tiled_ok=False: the aux tensor stays row-major.  -> (act, aux | None, aux_tiled)
+def _fc1_gelu(tp, b, x16, rows, stash, ln=True, tiled_ok=True):
+    act = _empty((rows, tp.Hd), tp.dt, tp.dev)
+    h, h_tiled = _aux_buf(rows, tp.Hd, tp.D, tp.dt, tp.dev, tiled_ok) if stash is not None else (None, False)
+    _gemm_fwd(x16, tp.D, [tp.P(b + "mlp.fc1.weight")], "w", act, bias=tp.P(b + "mlp.fc1.bias"), aux_out=h,
+              act=ops.ACT_GELU_SAVE_DERIV if stash == "pair" else ops.ACT_GELU, aux_tiled=h_tiled, ln=ln)
+    return act, h, h_tiled
+
+
+# fc2's weight gradient against the stored GELU output, then dH = (d16 W2) . gelu'(h) into that output's storage (dead after the weight
+# gradient) -> dH
+def _mlp_pair_backward(tp, b, a, d16):
+    linear_wgrad(d16, a["act"], tp.G(b + "mlp.fc2.weight"), tp.inv_s, dbias=tp.G(b + "mlp.fc2.bias"))
+    dh = a["act"]
+    _gemm_dx(d16, [tp.P(b + "mlp.fc2.weight")], "w", dh, ln=False, aux_in=a["h"], act=ops.ACT_MUL_AUX, aux_tiled=a["h_tiled"])   # a["h"] = gelu'(pre-activation)
+    return dh
+
+
+# LayerNorm `which` (1 | 2) of pre-norm block b over the kept frames of the stream x -> (GEMM operand, its 16-bit view, mean, rstd, the
+# rows the backward keeps as the LayerNorm input: fp16 normalised rows, the stream itself when every frame is kept, or the compact copy).
+def _prenorm_ln(tp, b, which, x, rows, fmap, mx8_for):
+    xh16 = tp.xh16
+    xc = _empty((rows, tp.D), torch.float32, tp.dev) if (fmap is not None and tp.save and not xh16) else None
+    xh = _empty((rows, tp.D), torch.float16, tp.dev) if xh16 else None
+    lnb, ln, mean, rstd = _ln16(x, tp.P(f"{b}norm{which}.weight"), tp.P(f"{b}norm{which}.bias"), tp.spec.eps, rows, tp.D, tp.dt, tp.dev,
+                                frame_map=fmap, rows_per_frame=tp.N, x_copy=xc, xhat=xh, mx8_for=mx8_for)
+    return lnb, ln, mean, rstd, xh if xh16 else (x if fmap is None else xc)
+
+
+# Activation diet: re-create LayerNorm `which`'s output from the saved rows a["x1" | "x2"] (fp32: the compact kept rows or the whole
+# stream, in either case exactly the rows the forward normalised; or their fp16 normalised form) -> (GEMM operand, its 16-bit view)
+def _prenorm_ln_again(tp, b, which, a, rows, mx8_for=None):
+    lnb, ln, _, _ = _ln16(a[f"x{which}"], tp.P(f"{b}norm{which}.weight"), tp.P(f"{b}norm{which}.bias"), tp.spec.eps, rows, tp.D, tp.dt, tp.dev,
+                          mx8_for=mx8_for, x_normalized=a["xn"])
+    return lnb, ln
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # The POST-norm block of EVA02-CLIP-bigE-14-plus (mico.py:341-344; eva_vit_model.py:411-413):
 #     x = x + drop_path(norm1(attn(x)));  x = x + drop_path(norm2(mlp(x)))
-# Off the ViT-g hot path - built from the hot path's kernels without its frame compaction, activation diet and
-# gradient hand-over: the branch input is a 16-bit cast of the fp32 stream, the branch output stays fp32 for its LayerNorm, every branch is
-# evaluated and scaled per frame (the reference's own drop_path schedule).
+# Off the ViT-g hot path (SURVEY section 8 row a7) - built from the hot path's launches without its frame compaction, activation diet and
+# gradient hand-over: the branch input is a 16-bit cast of the fp32 stream (ln=False), the branch output stays fp32 for its LayerNorm, every
+# branch is evaluated and scaled per frame on the host (the reference's own drop_path schedule).
 # ----------------------------------------------------------------------------------------------------------------------
-def _postnorm_block_forward(spec, P, b, x, Bf, dps, a, dt, dev, strides3):
-    D, N, H, hd, Hd = spec.D, spec.N, spec.H, spec.hd, spec.hidden
+def _postnorm_block_forward(tp, i, x, dps, a):
+    spec, P, dt, dev, Bf, N, D = tp.spec, tp.P, tp.dt, tp.dev, tp.Bf, tp.N, tp.D
+    b = f"blocks.{i}."
     M = Bf * N
 
     def branch_out(br, pre, sc):
@@ -546,35 +685,29 @@ def _postnorm_block_forward(spec, P, b, x, Bf, dps, a, dt, dev, strides3):
     # attention branch
     x16a = _empty((M, D), dt, dev)
     ops.cast_f32_to_16(x, x16a)
-    qb, vb = P(b + "attn.q_bias").detach(), P(b + "attn.v_bias").detach()
     qkv = _empty((M, 3 * D), dt, dev)
-    _gemm_fwd(x16a, D, [P(b + "attn.qkv.weight")], "qkv", qkv, bias=torch.cat((qb, torch.zeros_like(qb), vb)), ln=False)
-    ao = _empty((M, D), dt, dev)
-    lse = _empty((Bf, H, N), torch.float32, dev)
-    ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], ao, lse, B=Bf, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **strides3)
+    _gemm_fwd(x16a, D, [P(b + "attn.qkv.weight")], "qkv", qkv, bias=_qkv_bias(P, b), ln=False)
+    ao, lse = _self_attn_forward(tp, qkv, Bf)
     br1 = _empty((M, D), torch.float32, dev)
     _gemm_fwd(ao, D, [P(b + "attn.proj.weight")], "w", br1, bias=P(b + "attn.proj.bias"), ln=False)
-    sc1 = dps[0] if dps is not None else None
+    sc1, sc2 = (dps[0], dps[1]) if dps is not None else (None, None)
     x, mean1, rstd1 = branch_out(br1, "norm1", sc1)
     # MLP branch
     x16b = _empty((M, D), dt, dev)
     ops.cast_f32_to_16(x, x16b)
-    act, h = _empty((M, Hd), dt, dev), _empty((M, Hd), dt, dev)
-    _gemm_fwd(x16b, D, [P(b + "mlp.fc1.weight")], "w", act, bias=P(b + "mlp.fc1.bias"), aux_out=h, act=ops.ACT_GELU_SAVE_DERIV, ln=False)
+    act, h, h_tiled = _fc1_gelu(tp, b, x16b, M, "pair", ln=False, tiled_ok=False)
     br2 = _empty((M, D), torch.float32, dev)
-    _gemm_fwd(act, Hd, [P(b + "mlp.fc2.weight")], "w", br2, bias=P(b + "mlp.fc2.bias"), ln=False)
-    sc2 = dps[1] if dps is not None else None
+    _gemm_fwd(act, tp.Hd, [P(b + "mlp.fc2.weight")], "w", br2, bias=P(b + "mlp.fc2.bias"), ln=False)
     x, mean2, rstd2 = branch_out(br2, "norm2", sc2)
     a.update(post=True, x16a=x16a, qkv=qkv, ao=ao, lse=lse, br1=br1, mean1=mean1, rstd1=rstd1, sc1=sc1,
-             x16b=x16b, act=act, h=h, br2=br2, mean2=mean2, rstd2=rstd2, sc2=sc2)
+             x16b=x16b, act=act, h=h, h_tiled=h_tiled, br2=br2, mean2=mean2, rstd2=rstd2, sc2=sc2)
     return x
 
 
-def _postnorm_block_backward(spec, P, G, b, a, g, Bf, dt, dev, strides3, S):
+def _postnorm_block_backward(tp, b, a, g):
     """g: fp32 gradient of the residual stream [M, D] at the block's output, updated in place to the gradient at its input."""
-    D, N, H, hd, Hd = spec.D, spec.N, spec.H, spec.hd, spec.hidden
+    P, G, dt, dev, Bf, N, D, S, inv_s = tp.P, tp.G, tp.dt, tp.dev, tp.Bf, tp.N, tp.D, tp.S, tp.inv_s
     M = Bf * N
-    inv_s = 1.0 / S
 
     def branch_in(br, mean, rstd, pre, sc):
         """d(branch output), 16-bit in the gradient scale S: the LayerNorm backward of sc * g"""
@@ -586,60 +719,252 @@ def _postnorm_block_backward(spec, P, G, b, a, g, Bf, dt, dev, strides3, S):
 
     # MLP branch
     d16 = branch_in(a["br2"], a["mean2"], a["rstd2"], "norm2", a["sc2"])
-    w1, w2 = P(b + "mlp.fc1.weight"), P(b + "mlp.fc2.weight")
-    linear_wgrad(d16, a["act"], G(b + "mlp.fc2.weight"), inv_s, dbias=G(b + "mlp.fc2.bias"))
-    dh = a["act"]
-    _gemm_dx(d16, [w2], "w", dh, ln=False, aux_in=a["h"], act=ops.ACT_MUL_AUX)
+    dh = _mlp_pair_backward(tp, b, a, d16)
     linear_wgrad(dh, a["x16b"], G(b + "mlp.fc1.weight"), inv_s, dbias=G(b + "mlp.fc1.bias"))
-    _gemm_dx(dh, [w1], "w", g, ln=False, alpha=inv_s, resid=g)
+    _gemm_dx(dh, [P(b + "mlp.fc1.weight")], "w", g, ln=False, alpha=inv_s, resid=g)
     del d16, dh
     # attention branch
     d16 = branch_in(a["br1"], a["mean1"], a["rstd1"], "norm1", a["sc1"])
-    wp = P(b + "attn.proj.weight")
     linear_wgrad(d16, a["ao"], G(b + "attn.proj.weight"), inv_s, dbias=G(b + "attn.proj.bias"))
     dao = _empty((M, D), dt, dev)
-    _gemm_dx(d16, [wp], "w", dao, ln=False)
-    qkv = a["qkv"]
-    dqkv = _empty((M, 3 * D), dt, dev)
-    delta = _empty((Bf, H, N), torch.float32, dev)
-    ops.attn_bwd(qkv, qkv[:, D:], qkv[:, 2 * D:], a["ao"], dao, a["lse"], dqkv, dqkv[:, D:], dqkv[:, 2 * D:], delta,
-                 B=Bf, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **strides3)
+    _gemm_dx(d16, [P(b + "attn.proj.weight")], "w", dao, ln=False)
+    dqkv = _self_attn_backward(tp, a, dao, Bf)
     dbias = torch.zeros(3 * D, dtype=torch.float32, device=dev)
     linear_wgrad(dqkv, a["x16a"], G(b + "attn.qkv.weight"), inv_s, dbias=dbias)
-    G(b + "attn.q_bias").add_(dbias[:D])
-    G(b + "attn.v_bias").add_(dbias[2 * D:])
+    _qkv_bias_grad(G, b, dbias, D)
     _gemm_dx(dqkv, [P(b + "attn.qkv.weight")], "qkv", g, ln=False, alpha=inv_s, resid=g)
 
 
-def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None, keep=None):
-    """One pass of the tower over the frames in `groups`.  save=False keeps nothing for a backward (chunked forward).
-    diet (plain-MLP towers): 1 = the MLP intermediates are not kept (the backward recomputes fc1 + GELU / GELU'), 2 = nor the LayerNorm
-    outputs (recomputed from the saved fp32 rows) - see runtime.set_activation_diet.
-    keep (PatchKeep): patch dropout - the pass runs at keep.N tokens per frame (only the kept patches are embedded)."""
-    dt = runtime.compute_dtype()
-    P = lambda n: params[spec.idx[n]]
-    dev = params[0].device
-    D, N, np_, H, hd = spec.D, spec.N if keep is None else keep.N, spec.np, spec.H, spec.hd
-    arch = spec.arch
-    depth = arch["depth_built"]
-    Bf = sum(g.shape[0] for g in groups)
-    M = Bf * N
-    if keep is not None and arch.get("postnorm"):
-        raise NotImplementedError("patch dropout is not implemented for the post-norm tower (EVA02-CLIP-bigE-14-plus)")
-    if arch.get("postnorm"):
-        plan, diet = None, 0          # (the post-norm tower evaluates every branch and scales it: no frame compaction, no diet)
-        if dp_scale is not None:
-            dp_scale = dp_scale.detach().to(dev, torch.float32)
-    elif plan is None:
-        plan = DropPlan(dp_scale, Bf, dev) if dp_scale is not None else None
-    if arch["swiglu"]:
-        diet = 0      # (the SwiGLU towers keep everything: B/16 and L/14 frames are an order of magnitude smaller)
-    diet = TowerDiet.of(diet, depth)
-    xh16 = diet.xh16 and save
-    x = _empty((M, D), torch.float32, dev)
-    # ---- patch embedding: im2row + GEMM(+bias +pos, patch rows -> token rows) ; CLS rows ----
-    pe_w, pe_b, pos = P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed")
-    pos2 = pos.detach().reshape(spec.N, D)
+# ----------------------------------------------------------------------------------------------------------------------
+# The pre-norm blocks: x <- x + s1 * proj(attn(LN1 x));  x <- x + s2 * mlp(LN2 x), each branch on its kept frames only (DropPlan).
+# Attention with RoPE and the inner LayerNorm (sub-LN) for EVA02 B/16 and L/14; MLP: plain fc1 - GELU - fc2 with the activation diet
+# (g/14), or SwiGLU with its LayerNorm (EVA02).  Each forward puts what its backward reads into the block's dict `a` and returns the stream.
+# ----------------------------------------------------------------------------------------------------------------------
+def _attn_branch_forward(tp, i, x, a):
+    arch, P, N, D = tp.arch, tp.P, tp.N, tp.D
+    b = f"blocks.{i}."
+    B1, fmap1, sc1, tr1 = tp.branch_io(i, 0)
+    a.update(B1=B1, fmap1=fmap1, sc1=sc1, tr1=tr1)
+    if B1 <= 0:
+        return x
+    M1 = B1 * N
+    ln1b, ln1, mean1, rstd1, x1 = _prenorm_ln(tp, b, 1, x, M1, fmap1, 3 * D)
+    qkv_bias = _qkv_bias(P, b)
+    qkv = _empty((M1, 3 * D), tp.dt, tp.dev)
+    _gemm_fwd(ln1b, D, _qkv_params(P, b, arch), "qkv", qkv, bias=qkv_bias)
+    _rope_qk(tp, qkv, B1, fmap1)
+    ao, lse = _self_attn_forward(tp, qkv, B1)
+    proj_in = ao
+    if arch["subln"]:
+        proj_in, aln, mean_a, rstd_a = _ln16(ao, P(b + "attn.inner_attn_ln.weight"), P(b + "attn.inner_attn_ln.bias"),
+                                             tp.spec.eps, M1, D, tp.dt, tp.dev)
+        a.update(aln=aln, mean_a=mean_a, rstd_a=rstd_a)
+    x_mid = tp.stream_out(x, fmap1)
+    _gemm_fwd(proj_in, D, [P(b + "attn.proj.weight")], "w", x_mid, bias=P(b + "attn.proj.bias"), resid=x, row_scale=sc1,
+              rows_per_scale=N, row_map=fmap1, rows_per_map=N, ln=bool(arch["subln"]))
+    a.update(x1=x1, xn=tp.xh16, mean1=mean1, rstd1=rstd1, ln1=ln1 if tp.diet.keep_ln[i] else None, qkv=qkv, ao=ao, lse=lse)
+    return x_mid
+
+
+# g: fp32 gradient of the stream, updated in place;  pre: the hand-over from the block's MLP branch;  nxt: the saved dict of block
+# i - 1, whose MLP branch is next (None at block 0).  -> the hand-over to that branch
+def _attn_branch_backward(tp, b, a, g, pre, nxt):
+    if a["B1"] <= 0:
+        return None
+    arch, P, G, N, D, dt, dev, inv_s = tp.arch, tp.P, tp.G, tp.N, tp.D, tp.dt, tp.dev, tp.inv_s
+    B1, fmap1 = a["B1"], a["fmap1"]
+    M1 = B1 * N
+    g16 = tp.take_g16(g, pre, M1, fmap1, a["sc1"])
+    linear_wgrad(g16, a["aln"] if arch["subln"] else a["ao"], G(b + "attn.proj.weight"), inv_s, dbias=G(b + "attn.proj.bias"))
+    dao = _empty((M1, D), dt, dev)
+    _gemm_dx(g16, [P(b + "attn.proj.weight")], "w", dao, ln=bool(arch["subln"]))
+    if arch["subln"]:
+        dao2 = _empty((M1, D), dt, dev)
+        ops.layernorm_bwd(dao, a["ao"], P(b + "attn.inner_attn_ln.weight"), a["mean_a"], a["rstd_a"], dx16=dao2, grad_scale=inv_s, dtype=dt,
+                          dgamma=G(b + "attn.inner_attn_ln.weight"), dbeta=G(b + "attn.inner_attn_ln.bias"))
+        dao = dao2
+    fold1 = a["ln1"] is None and not arch["subln"] and _ln_fold_ok(a, dt)
+    if a["ln1"] is None and not fold1:      # activation diet: the LayerNorm output was not kept
+        a["ln1"] = _prenorm_ln_again(tp, b, 1, a, M1)[1]
+    dqkv = _self_attn_backward(tp, a, dao, B1)
+    _rope_qk(tp, dqkv, B1, fmap1, inverse=True)
+    dbias = torch.zeros(3 * D, dtype=torch.float32, device=dev)      # filled by the qkv weight-gradient launch below
+    if arch["subln"]:
+        dwf = torch.zeros((3 * D, D), dtype=torch.float32, device=dev)
+        linear_wgrad(dqkv, a["ln1"], dwf, inv_s, dbias=dbias)
+        for k, n in enumerate("qkv"):
+            G(b + f"attn.{n}_proj.weight").add_(dwf[k * D:(k + 1) * D])
+    elif fold1:     # against the kept normalised rows; norm1's gamma / beta applied to the [3 D, D] result
+        _wgrad_ln_folded(dqkv, a["x1"], P(b + "norm1.weight"), P(b + "norm1.bias"), G(b + "attn.qkv.weight"), None, inv_s, dbt=dbias)
+    else:
+        linear_wgrad(dqkv, a["ln1"], G(b + "attn.qkv.weight"), inv_s, dbias=dbias)
+    _qkv_bias_grad(G, b, dbias, D)
+    dln1 = _empty((M1, D), dt if runtime.CFG.ln_grad_16bit else torch.float32, dev)
+    _gemm_dx(dqkv, _qkv_params(P, b, arch), "qkv", dln1)
+    ho, pre = tp.handover(a["tr1"], nxt["B2"], nxt["sc2"], a["sc1"] is not None) if nxt is not None else ({}, None)
+    ops.layernorm_bwd(dln1, a["x1"], P(b + "norm1.weight"), a["mean1"], a["rstd1"], dy_scale=inv_s, dx_add=g, dx32=g, dtype=dt,
+                      dgamma=G(b + "norm1.weight"), dbeta=G(b + "norm1.bias"), frame_map=fmap1, rows_per_frame=N, x_normalized=a.get("xn", False), **ho)
+    return pre
+
+
+def _mlp_branch_forward(tp, i, x, a):
+    """The MLP branch of either pre-norm kind: LayerNorm 2 over the kept frames, the kind's MLP, its last GEMM's epilogue onto the stream."""
+    swiglu, N = tp.arch["swiglu"], tp.N
+    B2, fmap2, sc2, tr2 = tp.branch_io(i, 1)
+    a.update(B2=B2, fmap2=fmap2, sc2=sc2, tr2=tr2)
+    if B2 <= 0:
+        return x
+    M2 = B2 * N
+    ln2b, ln2, mean2, rstd2, x2 = _prenorm_ln(tp, f"blocks.{i}.", 2, x, M2, fmap2, None if swiglu else tp.Hd)
+    x_out = tp.stream_out(x, fmap2)
+    epi = dict(resid=x, row_scale=sc2, rows_per_scale=N, row_map=fmap2, rows_per_map=N)
+    (_swiglu_forward if swiglu else _plain_mlp_forward)(tp, i, ln2b, M2, x_out, epi, a)
+    diet = tp.diet
+    a.update(x2=x2, xn=tp.xh16, mean2=mean2, rstd2=rstd2, ln2=ln2 if diet.keep_ln[i] else None,
+             ln2b=ln2b if (diet.keep_ln[i] and not diet.keep_mlp[i]) else None)
+    return x_out
+
+
+# Kept frames only (a dropped branch has no gradient).  g: fp32 gradient of the stream, updated in place;  pre: the hand-over from
+# block i + 1's attention branch.  -> the hand-over to this block's attention branch
+def _mlp_branch_backward(tp, b, a, g, pre):
+    if a["B2"] <= 0:
+        return None
+    swiglu, P, G, N, D, dt = tp.arch["swiglu"], tp.P, tp.G, tp.N, tp.D, tp.dt
+    M2, fmap2 = a["B2"] * N, a["fmap2"]
+    g16 = tp.take_g16(g, pre, M2, fmap2, a["sc2"])
+    # gradient at the LayerNorm output: 16-bit like every other gradient operand (dqkv, dH, g16 carry the same scale) - the input-gradient
+    # GEMM writes half the bytes and the LayerNorm backward reads half; the SwiGLU path accumulates two GEMMs into it and stays fp32
+    dln2 = _empty((M2, D), torch.float32 if (swiglu or not runtime.CFG.ln_grad_16bit) else dt, tp.dev)
+    (_swiglu_backward if swiglu else _plain_mlp_backward)(tp, b, a, g16, dln2)
+    ho, pre = tp.handover(a["tr2"], a["B1"], a["sc1"], a["sc2"] is not None)
+    ops.layernorm_bwd(dln2, a["x2"], P(b + "norm2.weight"), a["mean2"], a["rstd2"], dy_scale=tp.inv_s, dx_add=g, dx32=g, dtype=dt,
+                      dgamma=G(b + "norm2.weight"), dbeta=G(b + "norm2.bias"), frame_map=fmap2, rows_per_frame=N, x_normalized=a.get("xn", False), **ho)
+    return pre
+
+
+def _plain_mlp_forward(tp, i, ln2b, M2, x_out, epi, a):
+    """fc1 - GELU - fc2 (g/14); what the block keeps of it is the diet's decision (TowerDiet.keep_mlp, .mlp_pre)."""
+    P, diet = tp.P, tp.diet
+    b = f"blocks.{i}."
+    if tp.save and diet.keep_mlp[i] and diet.mlp_pre:
+        act, a["h"], a["h_tiled"] = _fc1_gelu(tp, b, ln2b, M2, "pre")
+        a["pre"] = True
+    elif (tp.save and diet.keep_mlp[i]) or runtime.fp8_enabled() or not runtime.CFG.fc1_plain_gelu:   # (the 8-phase fp8 kernel has the pair epilogue only)
+        act, h, h_tiled = _fc1_gelu(tp, b, ln2b, M2, "pair")
+        if diet.keep_mlp[i]:
+            a.update(h=h, act=act, h_tiled=h_tiled)
+        del h
+    else:   # nobody will read GELU' (no backward, or the activation diet recomputes the pair)
+        act, _, _ = _fc1_gelu(tp, b, ln2b, M2, None)
+    _gemm_fwd(act, tp.Hd, [P(b + "mlp.fc2.weight")], "w", x_out, bias=P(b + "mlp.fc2.bias"), ln=False, **epi)
+
+
+def _plain_mlp_backward(tp, b, a, g16, dln2):
+    """dln2 <- the gradient at LayerNorm 2's output; fc1 / fc2 parameter gradients."""
+    P, G, D, Hd, dt, dev, inv_s = tp.P, tp.G, tp.D, tp.Hd, tp.dt, tp.dev, tp.inv_s
+    M2 = g16.shape[0]
+    w1, w2 = P(b + "mlp.fc1.weight"), P(b + "mlp.fc2.weight")
+    fold2 = False
+    kept_pre = bool(a.get("pre"))      # the block kept its fc1 pre-activation only (_mlp_keeps_pre)
+    if "act" not in a and not kept_pre:
+        # activation diet: the LayerNorm output (where it was not kept either), then fc1 + GELU / GELU' as the forward ran them
+        ln2b = a["ln2b"]
+        if ln2b is None:
+            ln2b, a["ln2"] = _prenorm_ln_again(tp, b, 2, a, M2, mx8_for=Hd)
+        a["act"], a["h"], a["h_tiled"] = _fc1_gelu(tp, b, ln2b, M2, "pair")
+        del ln2b
+    elif a["ln2"] is None:      # the MLP intermediates were kept, the LayerNorm output (fc1's weight gradient reads it) was not
+        fold2 = _ln_fold_ok(a, dt)   # ... and need not be: the gradient is taken against the normalised rows (below)
+        if not fold2:
+            a["ln2"] = _prenorm_ln_again(tp, b, 2, a, M2)[1]
+    if kept_pre:
+        # dH = (g16 W2) . gelu'(h) with gelu(h) re-created by the same epilogue - then fc2's weight gradient against it
+        dh, gact = _empty((M2, Hd), dt, dev), _empty((M2, Hd), dt, dev)
+        _gemm_dx(g16, [w2], "w", dh, ln=False, aux_in=a["h"], aux_out=gact, act=ops.ACT_GELU_GRAD, aux_tiled=a["h_tiled"])
+        a["h"] = None
+        linear_wgrad(g16, gact, G(b + "mlp.fc2.weight"), inv_s, dbias=G(b + "mlp.fc2.bias"))
+        del gact
+    else:
+        dh = _mlp_pair_backward(tp, b, a, g16)
+    if fold2:
+        _wgrad_ln_folded(dh, a["x2"], P(b + "norm2.weight"), P(b + "norm2.bias"), G(b + "mlp.fc1.weight"), G(b + "mlp.fc1.bias"), inv_s)
+    else:
+        linear_wgrad(dh, a["ln2"], G(b + "mlp.fc1.weight"), inv_s, dbias=G(b + "mlp.fc1.bias"))
+    _gemm_dx(dh, [w1], "w", dln2)
+
+
+def _swiglu_forward(tp, i, ln2b, M2, x_out, epi, a):
+    """w3 (ffn_ln (silu(w1 x) * w2 x)) (EVA02 B/16, L/14); everything is kept."""
+    spec, P, D, Hd, Hp, npad, dt, dev = tp.spec, tp.P, tp.D, tp.Hd, tp.Hp, tp.npad, tp.dt, tp.dev
+    b = f"blocks.{i}."
+    b1, b2 = _padv(P(b + "mlp.w1.bias"), Hp), _padv(P(b + "mlp.w2.bias"), Hp)
+    g1, g2 = _empty((M2, Hp), dt, dev), _empty((M2, Hp), dt, dev)
+    # parity configuration: the gate runs in fp32 (x1, x2 and the gated product never round to fp16 on the forward path); 16-bit copies
+    # of x1 / x2 are kept for the backward kernels only
+    split = runtime.split_precision()
+    x1, x2 = (_empty((M2, Hp), torch.float32, dev), _empty((M2, Hp), torch.float32, dev)) if split else (g1, g2)
+    _gemm_fwd(ln2b, D, [P(b + "mlp.w1.weight")], "w", x1, bias=b1, n_pad=npad)
+    _gemm_fwd(ln2b, D, [P(b + "mlp.w2.weight")], "w", x2, bias=b2, n_pad=npad)
+    hsw = _empty((M2, Hp), torch.float32 if split else dt, dev)
+    if split:
+        ops.swiglu_fwd_f32(x1, x2, hsw)
+        ops.cast_f32_to_16(x1, g1)
+        ops.cast_f32_to_16(x2, g2)
+    else:
+        ops.swiglu_fwd(g1, g2, hsw)
+    del x1, x2
+    hlnb, hln, mean_f, rstd_f = _ln16(hsw, _padv(P(b + "mlp.ffn_ln.weight"), Hp), _padv(P(b + "mlp.ffn_ln.bias"), Hp), spec.eps,
+                                      M2, Hp, dt, dev, valid_cols=Hd if npad else 0)
+    _gemm_fwd(hlnb, Hp, [P(b + "mlp.w3.weight")], "w", x_out, bias=P(b + "mlp.w3.bias"), k_pad=npad, **epi)
+    a.update(g1=g1, g2=g2, hsw=hsw, hln=hln, mean_f=mean_f, rstd_f=rstd_f)
+
+
+def _swiglu_backward(tp, b, a, g16, dln2):
+    """dln2 (fp32) <- the gradient at LayerNorm 2's output; w1 / w2 / w3 / ffn_ln parameter gradients."""
+    P, G, D, Hd, Hp, npad, dt, dev, inv_s = tp.P, tp.G, tp.D, tp.Hd, tp.Hp, tp.npad, tp.dt, tp.dev, tp.inv_s
+    M2 = g16.shape[0]
+    w1, w2, w3 = P(b + "mlp.w1.weight"), P(b + "mlp.w2.weight"), P(b + "mlp.w3.weight")
+    pend = []
+
+    def GP(name, shape):
+        """gradient target of `name`, or - padded hidden width - a zero-filled buffer of the padded shape whose leading
+        block is added to the parameter's gradient afterwards"""
+        tgt = G(name)
+        if npad is None:
+            return tgt
+        tmp = torch.zeros(shape, dtype=torch.float32, device=dev)
+        pend.append((tgt, tmp))
+        return tmp
+
+    linear_wgrad(g16, a["hln"], GP(b + "mlp.w3.weight", (D, Hp)), inv_s)
+    ops.colsum(g16, G(b + "mlp.w3.bias"), scale=inv_s, accumulate=True)
+    dhln = _empty((M2, Hp), dt, dev)
+    _gemm_dx(g16, [w3], "w", dhln, k_pad=npad)
+    dhsw = _empty((M2, Hp), dt, dev)
+    ops.layernorm_bwd(dhln, a["hsw"], _padv(P(b + "mlp.ffn_ln.weight"), Hp), a["mean_f"], a["rstd_f"], dx16=dhsw,
+                      dgamma=GP(b + "mlp.ffn_ln.weight", (Hp,)), dbeta=GP(b + "mlp.ffn_ln.bias", (Hp,)), grad_scale=inv_s,
+                      dtype=dt, valid_cols=Hd if npad else 0)
+    dx1, dx2 = dhln, _empty((M2, Hp), dt, dev)   # reuse dhln storage for dx1
+    ops.swiglu_bwd(a["g1"], a["g2"], dhsw, dx1, dx2)
+    linear_wgrad(dx1, a["ln2"], GP(b + "mlp.w1.weight", (Hp, D)), inv_s)
+    linear_wgrad(dx2, a["ln2"], GP(b + "mlp.w2.weight", (Hp, D)), inv_s)
+    ops.colsum(dx1, GP(b + "mlp.w1.bias", (Hp,)), scale=inv_s, accumulate=True)
+    ops.colsum(dx2, GP(b + "mlp.w2.bias", (Hp,)), scale=inv_s, accumulate=True)
+    _gemm_dx(dx1, [w1], "w", dln2, n_pad=npad)
+    _gemm_dx(dx2, [w2], "w", dln2, n_pad=npad, accumulate=True)
+    for tgt, tmp in pend:
+        tgt.add_(tmp[tuple(slice(0, n) for n in tgt.shape)])
+
+
+# ---- patch embedding: im2row + GEMM(+bias +pos, patch rows -> token rows) ; CLS rows ----
+def _patch_embed_forward(tp, groups):
+    """-> (the fp32 residual stream [Bf N, D], the 16-bit im2row rows per modality group - what the backward needs - when the pass saves)"""
+    spec, P, keep, dt, dev, Bf, N, D = tp.spec, tp.P, tp.keep, tp.dt, tp.dev, tp.Bf, tp.N, tp.D
+    np_ = spec.np
+    x = _empty((Bf * N, D), torch.float32, dev)
+    pe_w, pe_b = P("patch_embed.proj.weight"), P("patch_embed.proj.bias")
+    pos2 = P("pos_embed").detach().reshape(spec.N, D)
     saved_rows = []
     f0 = 0
     for g in groups:
@@ -656,142 +981,84 @@ def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None, keep
             rows16 = _empty((g.shape[0] * keep.k, kpad), dt, dev)
             ops.im2row_keep(g.contiguous().float(), rows16, keep.dev[f0:f0 + g.shape[0]], spec.P, kpad)
             ops.gemm(rows16, w16, x[f0 * N:], M=g.shape[0] * keep.k, N=D, K=kpad, bias=pe_b, remap=(keep.k, 1, 1), ksegs=ks)
-        if save:
+        if tp.save:
             saved_rows.append(rows16)
         f0 += g.shape[0]
     if keep is None:
         ops.cls_rows(x, Bf, N, P("cls_token").detach().reshape(D), pos2[0])
     else:
         ops.patch_pos_keep(x, keep.dev, P("cls_token").detach().reshape(D), pos2)
+    return x, saved_rows
 
-    def branch_io(i, which):
-        """-> (kept frames, frame list | None, scale vector | None)"""
-        return plan.branch(i, which) if plan is not None else (Bf, None, None)
 
-    def strides3():
-        return dict(q_strides=(N * 3 * D, 3 * D), k_strides=(N * 3 * D, 3 * D), v_strides=(N * 3 * D, 3 * D), o_strides=(N * D, D))
+def _patch_embed_backward(tp, saved, g):
+    """pos_embed / cls_token / patch_embed gradients from g, the fp32 gradient of the stream at the first block's input"""
+    spec, G, keep, dt, dev, N, D, inv_s = tp.spec, tp.G, tp.keep, tp.dt, tp.dev, tp.N, tp.D, tp.inv_s
+    if keep is None:
+        dpos = torch.zeros(N * D, dtype=torch.float32, device=dev)
+        ops.colsum(g, dpos, rows=tp.Bf, cols=N * D, ld=N * D)
+    else:     # patch dropout: each token's gradient lands on its own patch's table row (fixed-order sum over the frames, no atomics)
+        dpos = ops.pos_grad_keep(g, keep.dev, spec.np).view(-1)
+    G("pos_embed").add_(dpos.view(1, spec.N, D))
+    G("cls_token").add_(dpos[:D].view(1, 1, D))
+    PP = spec.P * spec.P
+    rows_pe = spec.np if keep is None else keep.k
+    f0 = 0
+    for (nf, C), rows16 in zip(saved["groups_meta"], saved["saved_rows"]):
+        gp16 = _empty((nf * rows_pe, D), dt, dev)
+        ops.gather_rows_cast(g[f0 * N:], gp16, remap=(rows_pe, 1, 1), scale=tp.S)
+        kpad = rows16.shape[1]
+        dw = torch.zeros((D, kpad), dtype=torch.float32, device=dev)
+        linear_wgrad(gp16, rows16, dw, inv_s)
+        c = 3 if C == 3 else 1      # (any other group ran on the channel-summed weight: its gradient broadcasts over the three channels)
+        G("patch_embed.proj.weight").add_(dw[:, :c * PP].reshape(D, c, spec.P, spec.P))
+        ops.colsum(gp16, G("patch_embed.proj.bias"), scale=inv_s, accumulate=True)
+        f0 += nf
+    saved["saved_rows"] = None
 
+
+def _tower_forward(spec, groups, dp_scale, params, save, diet=0, plan=None, keep=None):
+    """One pass of the tower over the frames in `groups`.  save=False keeps nothing for a backward (chunked forward).
+    diet (plain-MLP towers): 1 = the MLP intermediates are not kept (the backward recomputes fc1 + GELU / GELU'), 2 = nor the LayerNorm
+    outputs (recomputed from the saved fp32 rows) - see runtime.set_activation_diet.
+    keep (PatchKeep): patch dropout - the pass runs at keep.N tokens per frame (only the kept patches are embedded)."""
+    arch = spec.arch
+    depth, postnorm = arch["depth_built"], arch.get("postnorm")
+    dev = params[0].device
+    Bf = sum(g.shape[0] for g in groups)
+    if keep is not None and postnorm:
+        raise NotImplementedError("patch dropout is not implemented for the post-norm tower (EVA02-CLIP-bigE-14-plus)")
+    if postnorm:
+        plan, diet = None, 0          # (the post-norm tower evaluates every branch and scales it: no frame compaction, no diet)
+        if dp_scale is not None:
+            dp_scale = dp_scale.detach().to(dev, torch.float32)
+    elif plan is None:
+        plan = DropPlan(dp_scale, Bf, dev) if dp_scale is not None else None
+    if arch["swiglu"]:
+        diet = 0      # (the SwiGLU towers keep everything: B/16 and L/14 frames are an order of magnitude smaller)
+    tp = _TowerPass(spec, params, Bf, runtime.compute_dtype(), keep, plan=plan, diet=TowerDiet.of(diet, depth), save=save)
+    x, saved_rows = _patch_embed_forward(tp, groups)
     acts = []
-    Hd = spec.hidden
     pstate = runtime.snapshot()   # per-block precision: runtime.enter_block; the callers restore the pass-wide state
     for i in range(depth):
-        b = f"blocks.{i}."
         a = {}
         runtime.enter_block(i, pstate, bool(arch["swiglu"]), depth)
-        if _TAIL_EXP is not None:
-            runtime.CFG.split_fp16 = (i >= depth - _TAIL_EXP[0]) if _TAIL_EXP[0] >= 0 else (i < -_TAIL_EXP[0])
-            runtime.CFG.split_mode = _TAIL_EXP[1]
-        if arch.get("postnorm"):
-            x = _postnorm_block_forward(spec, P, b, x, Bf, dp_scale[i] if dp_scale is not None else None, a, dt, dev, strides3())
-            if save:
-                acts.append(a)
-            del a
-            continue
-        # --- attention branch: x <- x + s1 * proj(attn(LN1 x)) on the kept frames ---
-        B1, fmap1, sc1 = branch_io(i, 0)
-        a.update(B1=B1, fmap1=fmap1, sc1=sc1, tr1=plan.transition(i, 0) if plan is not None else None)
-        if B1 > 0:
-            M1 = B1 * N
-            xc1 = _empty((M1, D), torch.float32, dev) if (fmap1 is not None and save and not xh16) else None
-            xh1 = _empty((M1, D), torch.float16, dev) if xh16 else None
-            ln1b, ln1, mean1, rstd1 = _ln16(x, P(b + "norm1.weight"), P(b + "norm1.bias"), spec.eps, M1, D, dt, dev,
-                                            frame_map=fmap1, rows_per_frame=N, x_copy=xc1, xhat=xh1, mx8_for=3 * D)
-            qb, vb = P(b + "attn.q_bias").detach(), P(b + "attn.v_bias").detach()
-            qkv_bias = torch.cat((qb, torch.zeros_like(qb), vb))
-            qkv = _empty((M1, 3 * D), dt, dev)
-            _gemm_fwd(ln1b, D, _qkv_params(P, b, arch), "qkv", qkv, bias=qkv_bias)
-            if spec.rope is not None and keep is not None:      # each kept token rotates with its own patch's table row (rope.py:120-136)
-                ops.rope_keep(qkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1)
-                ops.rope_keep(qkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1)
-            elif spec.rope is not None:
-                ops.rope(qkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1])
-                ops.rope(qkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1])
-            ao = _empty((M1, D), dt, dev)
-            lse = _empty((B1, H, N), torch.float32, dev)
-            ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], ao, lse, B=B1, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **strides3())
-            proj_in = ao
-            if arch["subln"]:
-                proj_in, aln, mean_a, rstd_a = _ln16(ao, P(b + "attn.inner_attn_ln.weight"), P(b + "attn.inner_attn_ln.bias"),
-                                                     spec.eps, M1, D, dt, dev)
-                a.update(aln=aln, mean_a=mean_a, rstd_a=rstd_a)
-            # every frame kept: out of place, the input buffer itself is the saved LN input; otherwise the epilogue
-            # scatters the kept frames onto the stream in place and the LN's compact copy (xc1) is what is saved
-            # (with the fp16 normalised rows kept instead, nothing reads the stream again: in place either way)
-            x_mid = _empty((M, D), torch.float32, dev) if (fmap1 is None and save and not xh16) else x
-            _gemm_fwd(proj_in, D, [P(b + "attn.proj.weight")], "w", x_mid, bias=P(b + "attn.proj.bias"), resid=x, row_scale=sc1,
-                      rows_per_scale=N, row_map=fmap1, rows_per_map=N, ln=bool(arch["subln"]))
-            a.update(x1=xh1 if xh16 else (x if fmap1 is None else xc1), xn=xh16, mean1=mean1, rstd1=rstd1, ln1=ln1 if diet.keep_ln[i] else None,
-                     qkv=qkv, ao=ao, lse=lse)
-            x = x_mid
-        # --- MLP branch ---
-        B2, fmap2, sc2 = branch_io(i, 1)
-        a.update(B2=B2, fmap2=fmap2, sc2=sc2, tr2=plan.transition(i, 1) if plan is not None else None)
-        if B2 > 0:
-            M2 = B2 * N
-            xc2 = _empty((M2, D), torch.float32, dev) if (fmap2 is not None and save and not xh16) else None
-            xh2 = _empty((M2, D), torch.float16, dev) if xh16 else None
-            ln2b, ln2, mean2, rstd2 = _ln16(x, P(b + "norm2.weight"), P(b + "norm2.bias"), spec.eps, M2, D, dt, dev,
-                                            frame_map=fmap2, rows_per_frame=N, x_copy=xc2, xhat=xh2, mx8_for=None if arch["swiglu"] else spec.hidden)
-            x_out = _empty((M, D), torch.float32, dev) if (fmap2 is None and save and not xh16) else x
-            epi = dict(resid=x, row_scale=sc2, rows_per_scale=N, row_map=fmap2, rows_per_map=N)
-            if arch["swiglu"]:
-                Hp = spec.hidden_pad                     # == Hd unless the hidden width needs padding (see TowerSpec)
-                npad = Hp if Hp != Hd else None
-                b1, b2 = _padv(P(b + "mlp.w1.bias"), Hp), _padv(P(b + "mlp.w2.bias"), Hp)
-                g1, g2 = _empty((M2, Hp), dt, dev), _empty((M2, Hp), dt, dev)
-                if runtime.split_precision():
-                    # parity configuration: the gate runs in fp32 (x1, x2 and the gated product never round to fp16 on the
-                    # forward path); 16-bit copies of x1 / x2 are kept for the backward kernels only
-                    x1f, x2f = _empty((M2, Hp), torch.float32, dev), _empty((M2, Hp), torch.float32, dev)
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.w1.weight")], "w", x1f, bias=b1, n_pad=npad)
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.w2.weight")], "w", x2f, bias=b2, n_pad=npad)
-                    hsw = _empty((M2, Hp), torch.float32, dev)
-                    ops.swiglu_fwd_f32(x1f, x2f, hsw)
-                    ops.cast_f32_to_16(x1f, g1)
-                    ops.cast_f32_to_16(x2f, g2)
-                    del x1f, x2f
-                else:
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.w1.weight")], "w", g1, bias=b1, n_pad=npad)
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.w2.weight")], "w", g2, bias=b2, n_pad=npad)
-                    hsw = _empty((M2, Hp), dt, dev)
-                    ops.swiglu_fwd(g1, g2, hsw)
-                hlnb, hln, mean_f, rstd_f = _ln16(hsw, _padv(P(b + "mlp.ffn_ln.weight"), Hp), _padv(P(b + "mlp.ffn_ln.bias"), Hp), spec.eps,
-                                                  M2, Hp, dt, dev, valid_cols=Hd if npad else 0)
-                _gemm_fwd(hlnb, Hp, [P(b + "mlp.w3.weight")], "w", x_out, bias=P(b + "mlp.w3.bias"), k_pad=npad, **epi)
-                a.update(g1=g1, g2=g2, hsw=hsw, hln=hln, mean_f=mean_f, rstd_f=rstd_f)
-            else:
-                act = _empty((M2, Hd), dt, dev)
-                if save and diet.keep_mlp[i] and diet.mlp_pre:
-                    # the block keeps its pre-activation (2 hidden bytes per token): GELU with the pre-activation copy leaving from the registers
-                    h, h_tiled = _aux_buf(M2, Hd, D, dt, dev)
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.fc1.weight")], "w", act, bias=P(b + "mlp.fc1.bias"), aux_out=h, act=ops.ACT_GELU, aux_tiled=h_tiled)
-                    a.update(h=h, h_tiled=h_tiled, pre=True)
-                    del h
-                elif (save and diet.keep_mlp[i]) or runtime.fp8_enabled() or not runtime.CFG.fc1_plain_gelu:   # (the 8-phase fp8 kernel has the pair epilogue only)
-                    h, h_tiled = _aux_buf(M2, Hd, D, dt, dev)
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.fc1.weight")], "w", act, bias=P(b + "mlp.fc1.bias"), aux_out=h, act=ops.ACT_GELU_SAVE_DERIV, aux_tiled=h_tiled)
-                    if diet.keep_mlp[i]:
-                        a.update(h=h, act=act, h_tiled=h_tiled)
-                    del h
-                else:   # nobody will read GELU' (no backward, or the activation diet recomputes the pair): half the output bytes of the launch
-                    _gemm_fwd(ln2b, D, [P(b + "mlp.fc1.weight")], "w", act, bias=P(b + "mlp.fc1.bias"), act=ops.ACT_GELU)
-                _gemm_fwd(act, Hd, [P(b + "mlp.fc2.weight")], "w", x_out, bias=P(b + "mlp.fc2.bias"), ln=False, **epi)
-                del act
-            a.update(x2=xh2 if xh16 else (x if fmap2 is None else xc2), xn=xh16, mean2=mean2, rstd2=rstd2, ln2=ln2 if diet.keep_ln[i] else None,
-                     ln2b=ln2b if (diet.keep_ln[i] and not diet.keep_mlp[i]) else None)
-            x = x_out
+        if postnorm:
+            x = _postnorm_block_forward(tp, i, x, dp_scale[i] if dp_scale is not None else None, a)
+        else:
+            x = _attn_branch_forward(tp, i, x, a)
+            x = _mlp_branch_forward(tp, i, x, a)
         if save:
             acts.append(a)
         del a
     runtime.restore(pstate)
+    M, D = Bf * tp.N, tp.D
     out = _empty((M, D), torch.float32, dev)
     mean_n, rstd_n = _empty((M,), torch.float32, dev), _empty((M,), torch.float32, dev)
-    ops.layernorm_fwd(x, P("norm.weight"), P("norm.bias"), spec.eps, out32=out, mean=mean_n, rstd=rstd_n, dtype=dt)
-    saved = None
-    if save:
-        saved = dict(acts=acts, dt=dt, final=(x, mean_n, rstd_n), groups_meta=[(g.shape[0], g.shape[1]) for g in groups],
-                     saved_rows=saved_rows, Bf=Bf, keep=keep)
-    return out.view(Bf, N, D), saved
+    ops.layernorm_fwd(x, tp.P("norm.weight"), tp.P("norm.bias"), spec.eps, out32=out, mean=mean_n, rstd=rstd_n, dtype=tp.dt)
+    saved = dict(acts=acts, dt=tp.dt, final=(x, mean_n, rstd_n), groups_meta=[(g.shape[0], g.shape[1]) for g in groups],
+                 saved_rows=saved_rows, Bf=Bf, keep=keep) if save else None
+    return out.view(Bf, tp.N, D), saved
 
 
 def _tower_backward(spec, params, saved, dout, grads, final=True):
@@ -799,237 +1066,31 @@ def _tower_backward(spec, params, saved, dout, grads, final=True):
     final: no later pass adds to these gradients (last chunk) - finished blocks are then announced to runtime.grad_slice_hook."""
     hook = runtime.grad_slice_hook() if final else None
     block_range = spec.block_param_ranges()
-    dt = saved["dt"]
-    P = lambda n: params[spec.idx[n]]
-    dev = dout.device
-    keep = saved.get("keep")
-    D, N, np_, H, hd, Bf = spec.D, spec.N if keep is None else keep.N, spec.np, spec.H, spec.hd, saved["Bf"]
     arch = spec.arch
-    M = Bf * N
-    S = runtime.grad_scale()
-    inv_s = 1.0 / S
-
-    def G(name, like=None):
-        return grads.get(spec.idx[name])
-
-    def w16_of(p):
-        return runtime.gemm_weight([p])[0]
-
-    strides3 = dict(q_strides=(N * 3 * D, 3 * D), k_strides=(N * 3 * D, 3 * D), v_strides=(N * 3 * D, 3 * D),
-                    o_strides=(N * D, D))
+    tp = _TowerPass(spec, params, saved["Bf"], saved["dt"], saved.get("keep"), grads=grads)
+    M, D = tp.Bf * tp.N, tp.D
     x_last, mean_n, rstd_n = saved["final"]
-    g = _empty((M, D), torch.float32, dev)   # running gradient of the fp32 residual stream (updated in place)
-    ops.layernorm_bwd(dout.contiguous().view(M, D), x_last, P("norm.weight"), mean_n, rstd_n, dx32=g,
-                      dgamma=G("norm.weight"), dbeta=G("norm.bias"), dtype=dt)
+    g = _empty((M, D), torch.float32, tp.dev)   # running gradient of the fp32 residual stream (updated in place)
+    ops.layernorm_bwd(dout.contiguous().view(M, D), x_last, tp.P("norm.weight"), mean_n, rstd_n, dx32=g,
+                      dgamma=tp.G("norm.weight"), dbeta=tp.G("norm.bias"), dtype=tp.dt)
     saved["final"] = None
     del x_last
-    Hd = spec.hidden
     pstate = runtime.snapshot()
-    fuse = runtime.CFG.fuse_grad_handover
-
-    def take_g16(pre, rows, fmap, sc):
-        """The branch's 16-bit gradient operand [rows, D] = S * sc[frame] * g over its kept frames: handed over by the previous LayerNorm
-        backward (only the frames that branch did not keep are still gathered), or gathered whole."""
-        if pre is not None:
-            g16, dframes, ddst = pre
-            if dframes is not None and dframes.numel() > 0:
-                ops.gather_rows_cast(g, g16, row_scale=sc, rows_per_scale=N, scale=S, frame_map=dframes, rows_per_frame=N, dst_map=ddst)
-            return g16
-        g16 = _empty((rows, D), dt, dev)
-        ops.gather_rows_cast(g, g16, row_scale=sc, rows_per_scale=N, scale=S, frame_map=fmap, rows_per_frame=N)
-        return g16
-
-    def handover(tr, nb, nsc, had_plan):
-        """LayerNorm-backward arguments that make it write the next branch's operand (nb kept frames, per-frame scale nsc), and the `pre`
-        tuple for take_g16().  tr: DropPlan.transition of the current branch (None without a plan: both branches keep every frame)."""
-        if not fuse or nb <= 0 or (had_plan and tr is None):
-            return {}, None
-        g16n = _empty((nb * N, D), dt, dev)
-        if tr is None:
-            return dict(dx16=g16n, scale16=S), (g16n, None, None)
-        return dict(dx16=g16n, scale16=S, dx16_dst=tr[0], dx16_frame_scale=nsc), (g16n, tr[1], tr[2])
-
-    pre = None
+    pre = None      # hand-over of the 16-bit gradient operand from one branch's LayerNorm backward to the next branch (_TowerPass.handover)
     for i in reversed(range(arch["depth_built"])):
-        b = f"blocks.{i}."
-        a = saved["acts"].pop()
+        a, b = saved["acts"].pop(), f"blocks.{i}."
         runtime.enter_block(i, pstate, bool(arch["swiglu"]), arch["depth_built"])   # the block's weights in the layout its forward used
         if a.get("post"):
-            _postnorm_block_backward(spec, P, G, b, a, g, Bf, dt, dev, strides3, S)
-            del a
-            if hook is not None:
-                i0, i1 = block_range[i]
-                hook(grads.span(i0, i1), params[i0:i1])
-            continue
-        # ---------------- MLP branch (kept frames only: a dropped branch has no gradient) ----------------
-        if a["B2"] > 0:
-            M2, fmap2 = a["B2"] * N, a["fmap2"]
-            g16 = take_g16(pre, M2, fmap2, a["sc2"])
-            pre = None
-            # gradient at the LayerNorm output: 16-bit like every other gradient operand (dqkv, dH, g16 carry the same scale) - the input-gradient
-            # GEMM writes half the bytes and the LayerNorm backward reads half; the SwiGLU path accumulates two GEMMs into it and stays fp32
-            dln2 = _empty((M2, D), torch.float32 if (arch["swiglu"] or not runtime.CFG.ln_grad_16bit) else dt, dev)
-            if arch["swiglu"]:
-                w1, w2, w3 = P(b + "mlp.w1.weight"), P(b + "mlp.w2.weight"), P(b + "mlp.w3.weight")
-                Hp = spec.hidden_pad
-                npad = Hp if Hp != Hd else None
-                pend = []
-
-                def GP(name, shape):
-                    """gradient target of `name`, or - padded hidden width - a zero-filled buffer of the padded shape whose leading
-                    block is added to the parameter's gradient afterwards"""
-                    tgt = G(name)
-                    if npad is None:
-                        return tgt
-                    tmp = torch.zeros(shape, dtype=torch.float32, device=dev)
-                    pend.append((tgt, tmp))
-                    return tmp
-
-                linear_wgrad(g16, a["hln"], GP(b + "mlp.w3.weight", (D, Hp)), inv_s)
-                ops.colsum(g16, G(b + "mlp.w3.bias"), scale=inv_s, accumulate=True)
-                dhln = _empty((M2, Hp), dt, dev)
-                _gemm_dx(g16, [w3], "w", dhln, k_pad=npad)
-                dhsw = _empty((M2, Hp), dt, dev)
-                ops.layernorm_bwd(dhln, a["hsw"], _padv(P(b + "mlp.ffn_ln.weight"), Hp), a["mean_f"], a["rstd_f"], dx16=dhsw,
-                                  dgamma=GP(b + "mlp.ffn_ln.weight", (Hp,)), dbeta=GP(b + "mlp.ffn_ln.bias", (Hp,)), grad_scale=inv_s,
-                                  dtype=dt, valid_cols=Hd if npad else 0)
-                dx1, dx2 = dhln, _empty((M2, Hp), dt, dev)   # reuse dhln storage for dx1
-                ops.swiglu_bwd(a["g1"], a["g2"], dhsw, dx1, dx2)
-                linear_wgrad(dx1, a["ln2"], GP(b + "mlp.w1.weight", (Hp, D)), inv_s)
-                linear_wgrad(dx2, a["ln2"], GP(b + "mlp.w2.weight", (Hp, D)), inv_s)
-                ops.colsum(dx1, GP(b + "mlp.w1.bias", (Hp,)), scale=inv_s, accumulate=True)
-                ops.colsum(dx2, GP(b + "mlp.w2.bias", (Hp,)), scale=inv_s, accumulate=True)
-                _gemm_dx(dx1, [w1], "w", dln2, n_pad=npad)
-                _gemm_dx(dx2, [w2], "w", dln2, n_pad=npad, accumulate=True)
-                for tgt, tmp in pend:
-                    tgt.add_(tmp[tuple(slice(0, n) for n in tgt.shape)])
-                del dhln, dhsw, dx1, dx2, pend
-            else:
-                w1, w2 = P(b + "mlp.fc1.weight"), P(b + "mlp.fc2.weight")
-                fold2 = False
-                kept_pre = bool(a.get("pre"))      # the block kept its fc1 pre-activation only (_mlp_keeps_pre)
-                if "act" not in a and not kept_pre:
-                    # activation diet: the LayerNorm output (from the saved rows - fp32: compact kept rows or the whole stream, in either case
-                    # exactly the M2 rows the forward normalised; or their fp16 normalised form), then fc1 + GELU / GELU' as the forward ran them
-                    ln2b = a["ln2b"]
-                    if ln2b is None:
-                        ln2b, a["ln2"], _, _ = _ln16(a["x2"], P(b + "norm2.weight"), P(b + "norm2.bias"), spec.eps, M2, D, dt, dev, mx8_for=Hd,
-                                                     x_normalized=a["xn"])
-                    (a["h"], a["h_tiled"]), a["act"] = _aux_buf(M2, Hd, D, dt, dev), _empty((M2, Hd), dt, dev)
-                    _gemm_fwd(ln2b, D, [w1], "w", a["act"], bias=P(b + "mlp.fc1.bias"), aux_out=a["h"], act=ops.ACT_GELU_SAVE_DERIV, aux_tiled=a["h_tiled"])
-                    del ln2b
-                elif a["ln2"] is None:      # the MLP intermediates were kept, the LayerNorm output (fc1's weight gradient reads it) was not
-                    fold2 = _ln_fold_ok(a, dt)   # ... and need not be: the gradient is taken against the normalised rows (below)
-                    if not fold2:
-                        _, a["ln2"], _, _ = _ln16(a["x2"], P(b + "norm2.weight"), P(b + "norm2.bias"), spec.eps, M2, D, dt, dev, x_normalized=a["xn"])
-                if kept_pre:
-                    # dH = (g16 W2) . gelu'(h) with gelu(h) re-created by the same epilogue - then fc2's weight gradient against it
-                    dh, gact = _empty((M2, Hd), dt, dev), _empty((M2, Hd), dt, dev)
-                    _gemm_dx(g16, [w2], "w", dh, ln=False, aux_in=a["h"], aux_out=gact, act=ops.ACT_GELU_GRAD, aux_tiled=a["h_tiled"])
-                    a["h"] = None
-                    linear_wgrad(g16, gact, G(b + "mlp.fc2.weight"), inv_s, dbias=G(b + "mlp.fc2.bias"))
-                    del gact
-                else:
-                    linear_wgrad(g16, a["act"], G(b + "mlp.fc2.weight"), inv_s, dbias=G(b + "mlp.fc2.bias"))
-                    dh = a["act"]   # the GELU output is dead after the weight gradient: reuse its storage for dH
-                    _gemm_dx(g16, [w2], "w", dh, ln=False, aux_in=a["h"], act=ops.ACT_MUL_AUX, aux_tiled=a["h_tiled"])   # a["h"] = gelu'(pre-activation)
-                if fold2:
-                    _wgrad_ln_folded(dh, a["x2"], P(b + "norm2.weight"), P(b + "norm2.bias"), G(b + "mlp.fc1.weight"), G(b + "mlp.fc1.bias"), inv_s)
-                else:
-                    linear_wgrad(dh, a["ln2"], G(b + "mlp.fc1.weight"), inv_s, dbias=G(b + "mlp.fc1.bias"))
-                _gemm_dx(dh, [w1], "w", dln2)
-                del dh
-            ho, pre = handover(a["tr2"], a["B1"], a["sc1"], a["sc2"] is not None)
-            ops.layernorm_bwd(dln2, a["x2"], P(b + "norm2.weight"), a["mean2"], a["rstd2"], dy_scale=inv_s, dx_add=g,
-                              dx32=g, dgamma=G(b + "norm2.weight"), dbeta=G(b + "norm2.bias"), dtype=dt, frame_map=fmap2,
-                              rows_per_frame=N, x_normalized=a.get("xn", False), **ho)
-            del dln2, g16
+            _postnorm_block_backward(tp, b, a, g)
         else:
-            pre = None
-        # ---------------- attention branch ----------------
-        if a["B1"] > 0:
-            B1, fmap1 = a["B1"], a["fmap1"]
-            M1 = B1 * N
-            g16 = take_g16(pre, M1, fmap1, a["sc1"])
-            pre = None
-            wp = P(b + "attn.proj.weight")
-            proj_in = a["aln"] if arch["subln"] else a["ao"]
-            linear_wgrad(g16, proj_in, G(b + "attn.proj.weight"), inv_s, dbias=G(b + "attn.proj.bias"))
-            dao = _empty((M1, D), dt, dev)
-            _gemm_dx(g16, [wp], "w", dao, ln=bool(arch["subln"]))
-            if arch["subln"]:
-                dao2 = _empty((M1, D), dt, dev)
-                ops.layernorm_bwd(dao, a["ao"], P(b + "attn.inner_attn_ln.weight"), a["mean_a"], a["rstd_a"], dx16=dao2,
-                                  dgamma=G(b + "attn.inner_attn_ln.weight"), dbeta=G(b + "attn.inner_attn_ln.bias"),
-                                  grad_scale=inv_s, dtype=dt)
-                dao = dao2
-            fold1 = a["ln1"] is None and not arch["subln"] and _ln_fold_ok(a, dt)
-            if a["ln1"] is None and not fold1:      # activation diet: the LayerNorm output was not kept
-                _, a["ln1"], _, _ = _ln16(a["x1"], P(b + "norm1.weight"), P(b + "norm1.bias"), spec.eps, M1, D, dt, dev, x_normalized=a["xn"])
-            qkv = a["qkv"]
-            dqkv = _empty((M1, 3 * D), dt, dev)
-            delta = _empty((B1, H, N), torch.float32, dev)
-            ops.attn_bwd(qkv, qkv[:, D:], qkv[:, 2 * D:], a["ao"], dao, a["lse"], dqkv, dqkv[:, D:], dqkv[:, 2 * D:], delta,
-                         B=B1, H=H, Sq=N, Sk=N, hd=hd, scale=hd ** -0.5, **strides3)
-            if spec.rope is not None and keep is not None:
-                ops.rope_keep(dqkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1, inverse=True)
-                ops.rope_keep(dqkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], keep.dev, frame_map=fmap1, inverse=True)
-            elif spec.rope is not None:
-                ops.rope(dqkv, N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], inverse=True)
-                ops.rope(dqkv[:, D:], N * 3 * D, 3 * D, B1, N, H, hd, spec.rope[0], spec.rope[1], inverse=True)
-            dbias = torch.zeros(3 * D, dtype=torch.float32, device=dev)      # filled by the qkv weight-gradient launch below
-            if arch["subln"]:
-                dwf = torch.zeros((3 * D, D), dtype=torch.float32, device=dev)
-                linear_wgrad(dqkv, a["ln1"], dwf, inv_s, dbias=dbias)
-                G(b + "attn.q_proj.weight").add_(dwf[:D])
-                G(b + "attn.k_proj.weight").add_(dwf[D:2 * D])
-                G(b + "attn.v_proj.weight").add_(dwf[2 * D:])
-            elif fold1:     # against the kept normalised rows; norm1's gamma / beta applied to the [3 D, D] result
-                _wgrad_ln_folded(dqkv, a["x1"], P(b + "norm1.weight"), P(b + "norm1.bias"), G(b + "attn.qkv.weight"), None, inv_s, dbt=dbias)
-            else:
-                linear_wgrad(dqkv, a["ln1"], G(b + "attn.qkv.weight"), inv_s, dbias=dbias)
-            G(b + "attn.q_bias").add_(dbias[:D])
-            G(b + "attn.v_bias").add_(dbias[2 * D:])
-            dln1 = _empty((M1, D), dt if runtime.CFG.ln_grad_16bit else torch.float32, dev)
-            _gemm_dx(dqkv, _qkv_params(P, b, arch), "qkv", dln1)
-            nxt = saved["acts"][-1] if saved["acts"] else None     # block i - 1: its MLP branch is next
-            ho, pre = handover(a["tr1"], nxt["B2"], nxt["sc2"], a["sc1"] is not None) if nxt is not None else ({}, None)
-            ops.layernorm_bwd(dln1, a["x1"], P(b + "norm1.weight"), a["mean1"], a["rstd1"], dy_scale=inv_s, dx_add=g,
-                              dx32=g, dgamma=G(b + "norm1.weight"), dbeta=G(b + "norm1.bias"), dtype=dt, frame_map=fmap1,
-                              rows_per_frame=N, x_normalized=a.get("xn", False), **ho)
-            del dqkv, dao, dln1, g16
-        else:
-            pre = None
+            pre = _mlp_branch_backward(tp, b, a, g, pre)
+            pre = _attn_branch_backward(tp, b, a, g, pre, saved["acts"][-1] if saved["acts"] else None)
         del a
         if hook is not None:      # every gradient of block i is final: its arena slice can be reduced now
             i0, i1 = block_range[i]
             hook(grads.span(i0, i1), params[i0:i1])
     runtime.restore(pstate)
-    # ---------------- patch embedding ----------------
-    if keep is None:
-        dpos = torch.zeros(N * D, dtype=torch.float32, device=dev)
-        ops.colsum(g, dpos, rows=Bf, cols=N * D, ld=N * D)
-    else:     # patch dropout: each token's gradient lands on its own patch's table row (fixed-order sum over the frames, no atomics)
-        dpos = ops.pos_grad_keep(g, keep.dev, np_).view(-1)
-    G("pos_embed").add_(dpos.view(1, spec.N, D))
-    G("cls_token").add_(dpos[:D].view(1, 1, D))
-    pe_w = P("patch_embed.proj.weight")
-    PP = spec.P * spec.P
-    f0 = 0
-    for (nf, C), rows16 in zip(saved["groups_meta"], saved["saved_rows"]):
-        rows_pe = np_ if keep is None else keep.k
-        gp16 = _empty((nf * rows_pe, D), dt, dev)
-        ops.gather_rows_cast(g[f0 * N:], gp16, remap=(rows_pe, 1, 1), scale=S)
-        kpad = rows16.shape[1]
-        dw = torch.zeros((D, kpad), dtype=torch.float32, device=dev)
-        linear_wgrad(gp16, rows16, dw, inv_s)
-        if C == 3:
-            G("patch_embed.proj.weight").add_(dw[:, :3 * PP].reshape(D, 3, spec.P, spec.P))
-        else:
-            G("patch_embed.proj.weight").add_(dw[:, :PP].reshape(D, 1, spec.P, spec.P))
-        ops.colsum(gp16, G("patch_embed.proj.bias"), scale=inv_s, accumulate=True)
-        f0 += nf
-    saved["saved_rows"] = None
+    _patch_embed_backward(tp, saved, g)
     if hook is not None:              # what is left: embeddings, cls / pos, final norm (before and after the block parameters)
         for i0, i1 in spec.non_block_param_ranges():
             hook(grads.span(i0, i1), params[i0:i1])
@@ -1045,6 +1106,18 @@ def _slice_groups(groups, c0, c1):
             out.append(g[lo - f0:hi - f0])
         f0 = f1
     return out
+
+
+# The walk over a tower pass in chunks of `chunk` frames: per chunk (c0, c1, first, last, inputs), inputs = the (groups, dp_scale, keep)
+# of its _tower_forward call.  The LAST chunk is the one whose activations the forward keeps (they fit by construction); backward=True
+# walks from it down to the first - the others are recomputed - and has no inputs for it.
+def _tower_chunks(groups, dp_scale, keep, chunk, Bf, backward=False):
+    starts = list(range(0, Bf, chunk))
+    for c0 in (reversed(starts) if backward else starts):
+        c1, last = min(Bf, c0 + chunk), c0 == starts[-1]
+        inputs = None if (backward and last) else (_slice_groups(groups, c0, c1), dp_scale[:, :, c0:c1].contiguous() if dp_scale is not None else None,
+                                                   keep.slice(c0, c1) if keep is not None else None)
+        yield c0, c1, c0 == starts[0], last, inputs
 
 
 _SOFT_FRAC = float(os.environ.get("MICO_HBM_SOFT_FRAC", "0.87"))
@@ -1148,10 +1221,10 @@ def tower_plan(spec, n_frames, device, kept=1.0, block_tokens=None, n_tok=None):
                 # the margin)
                 left0 = budget - pf * n_frames - (_MLP_KEEP_MARGIN // 2 if (runtime.step_staged and exact) else _MLP_KEEP_MARGIN)
 
+                # (round 6, with ONE tensor per kept block nearly every block fits: the blocks whose recompute is dearest first - the
+                # head-split blocks' fc1 has twice the reduction length - then from the last block backwards; a block that does not fit is
+                # skipped, not the end.  The pair keeps round 5's measured order: from the last block backwards, stop at the first misfit.)
                 def fill(mlp_b):
-                    # (round 6, with ONE tensor per kept block nearly every block fits: the blocks whose recompute is dearest first - the
-                    # head-split blocks' fc1 has twice the reduction length - then from the last block backwards; a block that does not fit is
-                    # skipped, not the end.  The pair keeps round 5's measured order: from the last block backwards, stop at the first misfit.)
                     order = sorted(range(depth), key=lambda i: (-fc1_w[i], -i)) if mlp_b == 2 else list(reversed(range(depth)))
                     left, kp, sv = left0, [], 0.0
                     for i in order:
@@ -1184,11 +1257,6 @@ def tower_plan(spec, n_frames, device, kept=1.0, block_tokens=None, n_tok=None):
         # but none of its optional extras (MLP intermediates kept at level 3)
         best = (bh[0], bh[1], bh[2], bh[3] if (forced_diet is not None and bh[2] == 3) else None, bh[4])
     return best[1], TowerDiet(depth, best[2], keep=best[3] if best[2] == 3 else None, mlp_pre=best[4] if best[2] == 3 else False)
-
-
-def tower_chunk_frames(spec, n_frames, device, n_tok=None):
-    """Frames per tower pass (see tower_plan)."""
-    return tower_plan(spec, n_frames, device, n_tok=n_tok)[0]
 
 
 class EvaTowerFn(torch.autograd.Function):
@@ -1225,8 +1293,8 @@ class EvaTowerFn(torch.autograd.Function):
                 EvaTowerFn._logged_plan = (Bf, min(chunk, Bf), diet.level, tuple(diet.keep_mlp))
                 _log.info("tower plan: %d frames, %d per pass, activation diet %s (kept fraction %.3f)", Bf, min(chunk, Bf), diet.describe(), kept)
         ctx.spec, ctx.params, ctx.diet = spec, params, diet
-        if chunk >= Bf:
-            retry = False
+        retried = False
+        while chunk >= Bf:
             try:
                 out, ctx.saved = _tower_forward(spec, groups, dp_scale, params, save=needs_grad, diet=diet, plan=plan, keep=keep)
                 ctx.chunked = None
@@ -1236,42 +1304,32 @@ class EvaTowerFn(torch.autograd.Function):
                 # smaller device can under-estimate it.  The forward only wrote buffers of its own, so it is repeated ONCE on the next more
                 # conservative plan instead of failing the step.  Only the DECISION is taken here: while this handler is active the
                 # exception's traceback keeps the failed _tower_forward frame - its `acts`, `x`, every buffer of the failed attempt - alive,
-                # so empty_cache() would free nothing and the retry would allocate on top of them; the retry runs below, after
-                # the handler has exited and the traceback is gone.
-                if not needs_grad:
+                # so empty_cache() would free nothing and the retry would allocate on top of them; the next plan is chosen below
+                # and the loop runs it, after the handler has exited and the traceback is gone.
+                if retried or not needs_grad:
                     raise
-                retry = True
-            if retry:
-                ctx.saved = None
-                import gc
-                gc.collect()
-                torch.cuda.empty_cache()
-                dietable = not spec.arch["swiglu"] and not spec.arch.get("postnorm")
-                if dietable and runtime.activation_diet_override() is None and (diet.level < 3 or diet.mlp_blocks > 0):
-                    # next more conservative diet: no MLP intermediates at level 3, else the next level
-                    diet = TowerDiet(depth, 3) if diet.level == 3 else TowerDiet(depth, diet.level + 1)
-                else:
-                    chunk = -(-Bf // 2)
-                ctx.diet = diet
-                record(oom_retry=True)
-                _log.warning("tower pass ran out of memory: retrying with %d frames per pass, activation diet %s (rank-local decision)",
-                             min(chunk, Bf), diet.describe())
-                if chunk >= Bf:
-                    out, ctx.saved = _tower_forward(spec, groups, dp_scale, params, save=needs_grad, diet=diet, plan=plan, keep=keep)
-                    ctx.chunked = None
-                    return out
+                retried = True
+            ctx.saved = None
+            import gc
+            gc.collect()
+            torch.cuda.empty_cache()
+            dietable = not spec.arch["swiglu"] and not spec.arch.get("postnorm")
+            if dietable and runtime.activation_diet_override() is None and (diet.level < 3 or diet.mlp_blocks > 0):
+                # next more conservative diet: no MLP intermediates at level 3, else the next level
+                diet = TowerDiet(depth, 3) if diet.level == 3 else TowerDiet(depth, diet.level + 1)
+            else:
+                chunk = -(-Bf // 2)
+            ctx.diet = diet
+            record(oom_retry=True)
+            _log.warning("tower pass ran out of memory: retrying with %d frames per pass, activation diet %s (rank-local decision)",
+                         min(chunk, Bf), diet.describe())
         if plan is not None:      # the chunks draw their own plans from their slices of dp_scale: this one only priced the step
             DropPlan.stats[0] -= sum(plan.counts)
             DropPlan.stats[1] -= len(plan.counts) * Bf
         outs = []
         ctx.saved = None
-        starts = list(range(0, Bf, chunk))
-        for c0 in starts:
-            c1 = min(Bf, c0 + chunk)
-            sub_dp = dp_scale[:, :, c0:c1].contiguous() if dp_scale is not None else None
-            last = c0 == starts[-1]      # the last chunk's activations fit by construction: keep them, the backward starts there
-            o, saved = _tower_forward(spec, _slice_groups(groups, c0, c1), sub_dp, params, save=last, diet=diet,
-                                      keep=keep.slice(c0, c1) if keep is not None else None)
+        for _, _, _, last, inputs in _tower_chunks(groups, dp_scale, keep, chunk, Bf):
+            o, saved = _tower_forward(spec, *inputs[:2], params, save=last, diet=diet, keep=inputs[2])
             if last:
                 ctx.saved = saved
             outs.append(o)
@@ -1290,16 +1348,12 @@ class EvaTowerFn(torch.autograd.Function):
             runtime.mem_trace("tower backward end")
         else:
             groups, dp_scale, chunk, Bf, keep = ctx.chunked
-            starts = list(range(0, Bf, chunk))
-            for c0 in reversed(starts):      # last chunk first: its activations were kept by the forward, the others are recomputed
-                c1 = min(Bf, c0 + chunk)
-                if c0 == starts[-1]:
+            for c0, c1, first, last, inputs in _tower_chunks(groups, dp_scale, keep, chunk, Bf, backward=True):
+                if last:
                     saved, ctx.saved = ctx.saved, None
                 else:
-                    sub_dp = dp_scale[:, :, c0:c1].contiguous() if dp_scale is not None else None
-                    _, saved = _tower_forward(spec, _slice_groups(groups, c0, c1), sub_dp, params, save=True, diet=ctx.diet,
-                                              keep=keep.slice(c0, c1) if keep is not None else None)
-                _tower_backward(spec, params, saved, dout[c0:c1], grads, final=(c0 == starts[0]))
+                    _, saved = _tower_forward(spec, *inputs[:2], params, save=True, diet=ctx.diet, keep=inputs[2])
+                _tower_backward(spec, params, saved, dout[c0:c1], grads, final=first)
                 del saved
         return (None, None, None, None) + grads.result()
 

@@ -300,3 +300,50 @@ def test_tower_forward_oom_retry(cuda, monkeypatch):
         assert rel_err(o1, o0) < 1e-6       # (chunks draw per-chunk plans from the same masks: the same frames are kept)
         for n in g0:
             assert rel_err(g1[n], g0[n]) < 2e-3, (n, rel_err(g1[n], g0[n]))
+
+
+def test_tower_handover_and_mlp_stash_switches(cuda):
+    """The two branches of the plain-MLP tower's host code that no other tower-level test reaches: the gradient hand-over switched off
+    (every branch gathers its 16-bit gradient operand whole, runtime.CFG.fuse_grad_handover) and the GELU / GELU' pair as the kept blocks' stash
+    at activation-diet level 3 (runtime.CFG.mlp_keep_pre off).  g/14 architecture, depth 3, 5 frames with the injected masks: one fully skipped
+    MLP branch, one dropped frame, compacted rows.  The forward's values depend on none of it; the gradients differ by the summation order of
+    the fp32 atomics, by the fp16 rounding of the normalised rows (level 3) and - pre-activation against pair - by gelu / gelu' being
+    re-created from the 16-bit pre-activation instead of rounded from the fp32 accumulator: the bound test_activation_diet_recompute uses."""
+    from mico_amd import runtime as rt
+    depth, B = 3, 5
+    m, sd = build_model("evaclip01_giant", depth, device=cuda)
+    vis = m.vision_encoder.visual
+    g = torch.Generator().manual_seed(13)
+    img = torch.randn(B, 3, 224, 224, generator=g).to(cuda)
+    dps = _masks(depth, B, 0.7, 11)
+    w = (torch.randn(B, 257, 1408, generator=g) / (B * 257 * 1408) ** 0.5).to(cuda)
+    saved = (rt.CFG.fuse_grad_handover, rt.CFG.mlp_keep_pre)
+    settings = {"a": saved[:1] + (None, saved[1]), "b": (False, None, saved[1]), "c": (saved[0], (3, 2), False), "d": (saved[0], (3, 2), True)}
+    res = {}
+    try:
+        for tag, (fuse, diet, keep_pre) in settings.items():
+            rt.CFG.fuse_grad_handover, rt.CFG.mlp_keep_pre = fuse, keep_pre
+            rt.set_activation_diet(*diet) if diet is not None else rt.set_activation_diet(None)
+            with rt.precision(torch.float16):
+                m.zero_grad(set_to_none=True)
+                out = vis.forward_groups([img], drop_path_scale=dps)
+                plan = dict(rt.last_tower_plan)
+                (out * w).sum().backward()
+            if diet is not None:
+                assert (plan["diet"], plan["mlp_blocks_kept"]) == diet, plan
+                assert plan["mlp_stash"].startswith("pre-activation" if keep_pre else "gelu + gelu'"), plan
+            else:
+                assert plan["diet"] == 0, plan
+            res[tag] = (out.detach().clone(), {n: p.grad.clone() for n, p in vis.named_parameters() if p.grad is not None})
+    finally:
+        rt.CFG.fuse_grad_handover, rt.CFG.mlp_keep_pre = saved
+        rt.set_activation_diet(None)
+    for tag in "bcd":
+        assert torch.equal(res[tag][0], res["a"][0]), tag
+        assert set(res[tag][1]) == set(res["a"][1]), tag
+    for new, base in (("b", "a"), ("d", "c")):
+        errs = {n: rel_err(res[new][1][n], gb) for n, gb in res[base][1].items()}
+        worst = max(errs, key=errs.get)
+        print(f"gradients of ({new}) against ({base}): worst difference {errs[worst]:.3e} in {worst}")
+        for n, e in errs.items():
+            assert e < 2e-3, (new, base, n, e)

@@ -330,6 +330,21 @@ int mico_attn_decode_ws_bytes(int sets, int H, int QR, int Sk, int splits);
 int mico_attn_decode(const void* q, int64_t q_rs, const void* k, const void* v, int64_t kv_ss, int64_t kv_rs, void* o, int64_t o_rs,
                      const float* mask, int64_t mask_rs, int64_t mask_qs, int sets, int rows_per_set, int q_per_row, int H, int Sk,
                      int hd, float scale, int splits, float* ws, int64_t ws_bytes, int dtype, void* stream);
+/* Ragged sets (ABI 118; question answering - a sample's condition tokens are read by however many questions it has):
+ * mico_attn_decode with set s owning the query rows [set_row0[s], set_row0[s + 1]) instead of rows_per_set rows each.  set_row0: DEVICE
+ * int32 [sets + 1], ascending, set_row0[0] = 0, set_row0[sets] = rows; a set may be empty.  Query (row r, position i) is
+ * q[(r q_per_row + i) q_rs + h hd ..], its mask row mask[r mask_rs + i mask_qs ..] - the global row r, as in the uniform launch;
+ * keys / values of set s as there.  rows (the total) and max_rows_per_set (>= every set's row count; sizes the grid and the
+ * workspace) are checked against each other only: THE CALLER GUARANTEES THE TABLE, which the library cannot see - an entry outside
+ * [0, rows] or a set larger than max_rows_per_set reads / leaves unwritten rows it should not.  Chunks of 4 queries are counted from
+ * each set's first query and the key split is the uniform launch's, so a set's output equals mico_attn_decode over that set alone
+ * bit for bit; workgroups beyond a set's chunk count exit after reading the table (an empty set does no work); the split partials
+ * are folded in split order (bit-identical from run to run).  Workspace: mico_attn_decode_ragged_ws_bytes(...) bytes (0 / -1 as above). */
+int mico_attn_decode_ragged_ws_bytes(int sets, int H, int max_rows_per_set, int q_per_row, int Sk, int splits);
+int mico_attn_decode_ragged(const void* q, int64_t q_rs, const void* k, const void* v, int64_t kv_ss, int64_t kv_rs, void* o, int64_t o_rs,
+                            const float* mask, int64_t mask_rs, int64_t mask_qs, int sets, const int* set_row0, int rows,
+                            int max_rows_per_set, int q_per_row, int H, int Sk, int hd, float scale, int splits, float* ws,
+                            int64_t ws_bytes, int dtype, void* stream);
 /* K/V-cache upkeep (16-bit elements, 16-byte aligned, widths / strides multiples of 8):
  * append:  cache[r cache_ss + (pos0 + i) cache_rs + c] = src[(r n_new + i) src_rs + c]   (r < rows, i < n_new, c < width);
  * gather:  dst[l layer_stride + r row_stride + e] = src[l layer_stride + parent[r] row_stride + e]   (l < layers, r < rows, e < n;

@@ -99,11 +99,12 @@ def write_synthetic_pretrain_dir(path, vision_encoder_type="evaclip01_giant", st
 
 
 @torch.no_grad()
-def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False, rerank=False):
+def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False, rerank=False, questions=None):
     """The retrieval + matching part of the reference's __main__ (inference_demo.py:128-158).  use_cache: the caption's beam search
     decodes incrementally (BertForMaskedLM.generate(use_cache=True)).  rerank: the ITM scores come from the retrieval evaluation path
     (mico_amd.evaluation.rerank_retrieval: the image's condition tokens projected once, every text reading them by index) instead of one
-    copy of the tokens per text - the same scores."""
+    copy of the tokens per text - the same scores.  questions (list[str]; None: none asked): the image's answers to them
+    (MiCo.forward_qa, vast.py:557-650) as "answers" - with use_cache the image's condition tokens are projected once for all questions."""
     image_input = image_input.to(device).unsqueeze(1)          # image as a 1 frame video
     video_output = model.forward_vision_encoder(image_input)
     feat_v = F.normalize(model.contra_head_v(model.pool_vision_for_contra(video_output)), dim=-1)
@@ -133,8 +134,18 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=
                                                 num_beams=model.beam_size, eos_token_id=tk.sep_token_id,
                                                 pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=use_cache)
     captions = tk.batch_decode(outputs[:, 1:], skip_special_tokens=True)
-    return dict(feat_v=feat_v, feat_t=feat_t, sim_t2v=sim_t2v, itm_scores=slice_scores, input_ids=input_ids,
-                caption_ids=outputs, captions=captions)
+    out = dict(feat_v=feat_v, feat_t=feat_t, sim_t2v=sim_t2v, itm_scores=slice_scores, input_ids=input_ids,
+               caption_ids=outputs, captions=captions)
+    if questions:
+        # every question is asked of the one image: one sample with len(questions) questions
+        before = model.config.get("decode_use_cache", False)
+        model.config["decode_use_cache"] = bool(use_cache)
+        try:
+            qa = model.forward_qa({"vision_pixels": image_input, "raw_questions": [list(questions)]}, "qa%tv", compute_loss=False)
+        finally:
+            model.config["decode_use_cache"] = before
+        out["answers"] = qa["generated_answers_tv"]
+    return out
 
 
 def main():
@@ -143,6 +154,7 @@ def main():
     ap.add_argument("--synthetic", default=None, help="vision_encoder_type: build a synthetic pretrain dir instead of reading one")
     ap.add_argument("--image", default="example/test.jpeg")
     ap.add_argument("--texts", nargs="*", default=["a man is skiing in a snowy day.", "it's a hot day"])
+    ap.add_argument("--question", action="append", default=None, help="a question about the image (repeatable); the answers are printed")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--use_cache", action="store_true", help="decode the caption incrementally (K/V cache; same caption)")
     ap.add_argument("--rerank", action="store_true", help="ITM scores through the retrieval evaluation path (indexed K/V memory; same scores)")
@@ -161,10 +173,12 @@ def main():
     image_input = proc(args.image)
     if image_input is None:
         raise SystemExit(f"cannot read {args.image}")
-    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache, rerank=args.rerank)
+    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache, rerank=args.rerank, questions=args.question)
     print(out["sim_t2v"])
     print(out["itm_scores"])
     print(out["captions"])
+    if args.question:
+        print(out["answers"])
 
 
 if __name__ == "__main__":

@@ -81,6 +81,9 @@ PROTOTYPES = {
     "mico_attn_decode_ws_bytes": [c_int, c_int, c_int, c_int, c_int],
     "mico_attn_decode": [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_f, c_int, c_vp, c_i64, c_int, c_vp],
+    "mico_attn_decode_ragged_ws_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "mico_attn_decode_ragged": [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_f, c_int, c_vp, c_i64, c_int, c_vp],
     "mico_decode_kv_append": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp],
     "mico_decode_kv_gather": [c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp],
     "mico_rope": [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
@@ -144,7 +147,7 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 117   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 118   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):

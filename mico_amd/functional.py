@@ -2283,7 +2283,8 @@ class BertDecodeCache:
     token) and t (the new [MASK]).  The cache keeps:
       kv      per-layer self-attention K / V of every row, [L, rows, max_len, 2 D] (a second buffer for the beam re-gather);
       kvx     cross-attention K / V of the condition tokens, projected ONCE PER CONDITION SET: [sets E, L * 2 D] (CrossKVFn's interleaved
-              layout), read by the rows_per_set rows of a set (beams, or sampled captions) through mico_attn_decode;
+              layout), read by the rows_per_set rows of a set (beams, or sampled captions) through mico_attn_decode - or, with a
+              SEQUENCE rows_per_set (a sample's questions x beams), by set s's rows_per_set[s] rows through mico_attn_decode_ragged;
       mask    the additive mask (extended_attention_mask) of the fully grown 3-D mask, [rows, max_len, max_len] fp32.
     The first pass (prefill) runs the prompt plus [MASK] (all prompt positions), every later pass 2 rows per sequence; only the [MASK]
     row goes through the LM head.  Precision: runtime.compute_dtype() / split_activations() as BertFn."""
@@ -2293,7 +2294,8 @@ class BertDecodeCache:
     def __init__(self, spec, params, head, cond, rows_per_set, mask, mask_token_id):
         """params: BertModel's parameters in spec order; head: the LM head's (transform W, b, LN gamma, beta, decoder W, b);
         cond: fp32 [sets, E, D] condition tokens or None; mask: {0, 1} [rows, max_len, max_len], the prompt's 3-D mask grown to the
-        longest sequence the decode reaches (rows = sets * rows_per_set, sample-major)."""
+        longest sequence the decode reaches (rows = sets * rows_per_set, sample-major; rows_per_set a list / tuple: one row count per set,
+        zero allowed, rows = their sum)."""
         if any(p.requires_grad for p in params) and torch.is_grad_enabled():
             raise RuntimeError("BertDecodeCache is an inference feature: call under torch.no_grad()")
         # (the parameter objects themselves, not detached views: runtime's 16-bit weight cache is keyed on the object - a fresh view per
@@ -2305,10 +2307,20 @@ class BertDecodeCache:
         D, L = spec.D, spec.L
         self.dt = dt = runtime.compute_dtype()
         self.rows, self.max_len = mask.shape[0], mask.shape[1]
-        self.R = int(rows_per_set)
-        if self.rows % self.R:
-            raise ValueError(f"BertDecodeCache: {self.rows} rows are not a whole number of sets of {self.R}")
-        self.sets = self.rows // self.R
+        self.set_row0 = None
+        if isinstance(rows_per_set, (list, tuple)):
+            # ragged sets (question answering: a sample's rows = its questions x beams): the first-row table is built here on the host from
+            # the Python list and copied once; R is the largest set, which sizes the cross-attention launch
+            table = self.set_row_table(rows_per_set)
+            if int(table[-1]) != self.rows:
+                raise ValueError(f"BertDecodeCache: sets of {list(rows_per_set)} rows do not add up to the {self.rows} rows of the mask")
+            self.sets, self.R = len(rows_per_set), max(int(r) for r in rows_per_set)
+            self.set_row0 = table.to(dev)
+        else:
+            self.R = int(rows_per_set)
+            if self.rows % self.R:
+                raise ValueError(f"BertDecodeCache: {self.rows} rows are not a whole number of sets of {self.R}")
+            self.sets = self.rows // self.R
         if self.max_len > P("embeddings.position_embeddings.weight").shape[0]:
             raise ValueError(f"BertDecodeCache: {self.max_len} positions exceed the position table")
         self.mask = ((1.0 - mask.to(torch.float32)) * -10000.0).contiguous()
@@ -2325,6 +2337,11 @@ class BertDecodeCache:
             ops.cast_f32_to_16(cond.float().contiguous().view(self.sets * E, D), cond16)
             self.kvx = _empty((self.sets * E, L * 2 * D), dt, dev)
             _project_kv_all(cond16, cross_kv_params(spec, params), L, self.kvx)
+
+    @staticmethod
+    def set_row_table(rows_per_set):
+        """Host int32 [sets + 1] first-row table of ragged sets: (3, 0, 6) -> [0, 3, 3, 9] (mico_attn_decode_ragged's set_row0)."""
+        return ops.decode_set_row0(rows_per_set)
 
     def reorder(self, parent):
         """Beam search: row r continues the prefix of row parent[r] (int64 [rows]) - the cached positions that stay, [0, filled - 1),
@@ -2387,6 +2404,10 @@ class BertDecodeCache:
             cc = _empty((N, D), dt, dev)
             kvl = self.kvx[:, li * 2 * D:]
             # the rows_per_set x n queries of a condition set share its keys
+            if self.set_row0 is not None:
+                ops.attn_decode_ragged(q, kvl, kvl[:, D:], cc, set_row0=self.set_row0, rows=rows, max_rows_per_set=self.R, q_per_row=n, H=H,
+                                       Sk=self.E, hd=hd, scale=scale, q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
+                return cc, None
             ops.attn_decode(q, kvl, kvl[:, D:], cc, sets=self.sets, rows_per_set=self.R, q_per_row=n, H=H, Sk=self.E, hd=hd, scale=scale,
                             q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
             return cc, None

@@ -287,7 +287,8 @@ class BertForMaskedLM(nn.Module):
 
     def _decode_cache(self, input_ids, attention_mask, cond, rows_per_set, max_length):
         """functional.BertDecodeCache for a decode of input_ids / attention_mask ([rows, n], [rows, n, n]) that reaches max_length
-        positions; cond [rows / rows_per_set, E, D] (one condition set per rows_per_set consecutive rows) or None."""
+        positions; cond [rows / rows_per_set, E, D] (one condition set per rows_per_set consecutive rows; rows_per_set a list: set s is
+        read by rows_per_set[s] consecutive rows) or None."""
         mask = attention_mask
         while mask.shape[1] < max_length:
             mask = self.update_attention_mask(mask)
@@ -297,7 +298,7 @@ class BertForMaskedLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, max_new_tokens=20, num_beams=1,
                  eos_token_id=None, pad_token_id=None, length_penalty=1.0, do_sample=False, top_k=50, sample_noise=None,
-                 use_cache=False, num_return_sequences=1, **unused):
+                 use_cache=False, num_return_sequences=1, rows_per_condition=None, **unused):
         """Beam search with the semantics of transformers==4.31 GenerationMixin.generate / BeamSearchScorer as the reference
         calls it (inference_demo.py:164-171: num_beams 3, length_penalty 0.6, early_stopping False, no logits processors):
         2*num_beams candidates per step, finished hypotheses scored sum_logprob / len**length_penalty, the "cannot improve"
@@ -305,9 +306,25 @@ class BertForMaskedLM(nn.Module):
         the host over 2*num_beams candidates per sample; the model step and log-softmax / top-k run on the device.
         use_cache: incremental decoding (functional.BertDecodeCache) - one pass over the prompt, then 2 positions per row and step;
         the rows of one condition set (beams, sampled captions) share its cross-attention K/V.  Same ids as the recomputing path up to
-        floating-point reduction order.  num_return_sequences (sampling only): n rows per condition set, sample-major."""
+        floating-point reduction order.  num_return_sequences (sampling only): n rows per condition set, sample-major.
+        rows_per_condition (beam search only; None: one prompt row per condition set): a sequence of ints, one per set of
+        encoder_hidden_states - set s is read by rows_per_condition[s] consecutive prompt rows (question answering: a sample's questions;
+        zero allowed).  With the cache each set is projected once and read through the ragged decode attention; without it the condition
+        tokens are expanded here, one copy per prompt row."""
         if unused:
             raise TypeError(f"generate(): unsupported arguments {sorted(unused)}")
+        rpc = None
+        if rows_per_condition is not None:      # (checked before anything is launched)
+            rpc = [int(r) for r in rows_per_condition]
+            if do_sample:
+                raise ValueError("generate(): rows_per_condition is provided for beam search only")
+            if encoder_hidden_states is None or len(rpc) != encoder_hidden_states.shape[0]:
+                raise ValueError(f"generate(): rows_per_condition has {len(rpc)} entries for "
+                                 f"{0 if encoder_hidden_states is None else encoder_hidden_states.shape[0]} condition sets")
+            if any(r < 0 for r in rpc):
+                raise ValueError(f"generate(): rows_per_condition {rpc} holds a negative row count")
+            if sum(rpc) != input_ids.shape[0]:
+                raise ValueError(f"generate(): rows_per_condition {rpc} adds up to {sum(rpc)}, the prompt has {input_ids.shape[0]} rows")
         nrs = int(num_return_sequences)
         if nrs < 1 or (nrs != 1 and not do_sample):
             raise ValueError("generate(): num_return_sequences > 1 is provided for sampling (do_sample=True) only")
@@ -329,8 +346,14 @@ class BertForMaskedLM(nn.Module):
         max_length = cur + int(max_new_tokens)
         ids = input_ids.repeat_interleave(nb, dim=0)
         mask = attention_mask.repeat_interleave(nb, dim=0)
-        dec = self._decode_cache(ids, mask, encoder_hidden_states, nb, max_length) if use_cache else None
-        enc = encoder_hidden_states.repeat_interleave(nb, dim=0).contiguous() if encoder_hidden_states is not None and dec is None else None
+        dec = self._decode_cache(ids, mask, encoder_hidden_states, nb if rpc is None else [r * nb for r in rpc], max_length) if use_cache else None
+        enc = None
+        if encoder_hidden_states is not None and dec is None:
+            if rpc is None:
+                enc = encoder_hidden_states.repeat_interleave(nb, dim=0).contiguous()
+            else:    # (the row -> set index is built on the host: no device-side size query)
+                own = torch.arange(len(rpc)).repeat_interleave(torch.tensor(rpc) * nb)
+                enc = encoder_hidden_states[own.to(dev)].contiguous()
         beam_scores = torch.zeros(B, nb, dtype=torch.float32, device=dev)
         beam_scores[:, 1:] = -1e9
         beam_scores = beam_scores.view(-1)

@@ -327,6 +327,7 @@ class MiCo(MMGeneralModule):
         self.max_omni_caption_len = c.max_omni_caption_len
         self.max_caption_len = c.max_caption_len
         self.max_subtitle_len = c.max_subtitle_len
+        self.max_answer_len = int(c.get("max_answer_len", 10))    # answers' token length and the answer decode's max_new_tokens (vast.py:583,639)
         tok = self.multimodal_encoder.tokenizer
         self.text_masker = TokenMasker(mask_token=tok.mask_token_id, range_start=106, range_end=30522)
 
@@ -344,4 +345,4 @@ class MiCo(MMGeneralModule):
     # forward(batch, task, compute_loss): task grammar "ret%tv%ta..._cap%tv..." (vast.py:317-348); sub-task letters
     # v = vision (image/video), a = audio, d = depth; fused conditions "va" (contra_head_va) and "vd" (contra_head_id).
     # ------------------------------------------------------------------------------------------------------------------
-    from .mico_forward import forward, encode_batch, _feat_cond, _condition_feats   # noqa: E402,F401
+    from .mico_forward import forward, forward_qa, encode_batch, _feat_cond, _condition_feats   # noqa: E402,F401

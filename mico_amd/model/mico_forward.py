@@ -3,11 +3,13 @@
 Specification: the VAST sibling's trainer-facing forward (data/model/vast.py:317-348), forward_ret (:383-464: ITC with
 label smoothing 0.1 against the all-gathered global batch, ITM with in-batch hard negatives) and forward_cap (:485-512:
 causal masked-caption LM), generalised with MiCo's depth heads (model/mico.py:390,392,402,406).  These functions become
-methods of mico_amd.model.mico.MiCo.
+methods of mico_amd.model.mico.MiCo.  The question-answering family ("qa%...", vast.py:557-650) has an entry of its own: forward_qa below.
 
 batch keys: vision_pixels [b,n,3,h,w] | audio_spectrograms [b,n,h,w] | depth_pixels [b,n,3,h,w] (any subset);
             raw_captions (list[str]) or input_ids/attention_mask [b,S].
-            optional `_injected`: {subtask: {neg_cond_idx, neg_text_idx}, "cap": {masked_ids, labels}} replaces the RNG draws
+            forward_qa: raw_questions (list[str]; evaluation: or list[list[str]]) / raw_answers, or question_ids / question_mask
+            [nq, Lq] (+ num_questions, list[int], for several questions per sample) and answer_ids / answer_mask [b, La].
+            optional `_injected`: {subtask: {neg_cond_idx, neg_text_idx}, "cap" / "qa": {masked_ids, labels}} replaces the RNG draws
             (torch.multinomial / TokenMasker) for parity tests, "drop_path_scale" / "patch_keep" ({modality: [depth, 2, b*n] /
             int [b*n, keep]}) the tower's stochastic-depth and patch-dropout draws; optional `_world`: simulated gathered tensors.
 """
@@ -20,6 +22,7 @@ from .. import runtime
 COND_MODALITY = {"v": "vision", "a": "audio", "d": "depth"}
 FUSED_HEADS = {"v": "contra_head_v", "a": "contra_head_a", "d": "contra_head_d", "s": "contra_head_s", "va": "contra_head_va",
                "vd": "contra_head_id", "vs": "contra_head_vs", "vas": "contra_head_vas"}
+_UNKNOWN_FAMILY = "{}: MiCo.forward runs the ret% / itc% / cap% families; question answering (qa%...) is MiCo.forward_qa"
 SUBTASKS = ("tv", "ta", "td", "ts", "tva", "tvd", "tvs", "tvas")    # vast.py's tv / ta / tva / tvs / tvas + MiCo's depth heads
 
 
@@ -213,6 +216,102 @@ def _forward_cap(self, batch, enc, subtasks):
     return {"loss_cap": sum(losses) / len(losses)}
 
 
+def qa_attention_mask(question_mask, answer_mask):
+    """The part-causal 3-D mask of the QA pass (vast.py:594-599) from the key-padding masks [b, Lq], [b, La] -> {0, 1} [b, Lq + La, Lq + La]:
+    padded keys are hidden from every row, question rows see the question only (bidirectional), answer rows see the question and the answer
+    positions up to their own (prefix LM)."""
+    Lq = question_mask.shape[1]
+    keys = torch.cat((question_mask, answer_mask), dim=1)
+    S = keys.shape[1]
+    see = torch.ones(S, S, dtype=keys.dtype, device=keys.device).tril_()     # key j <= query i ...
+    see[:, :Lq] = 1                                                          # ... or key j in the question
+    return (keys.unsqueeze(1) * see.unsqueeze(0)).contiguous()
+
+
+def _qa_questions(self, batch):
+    """question ids / mask [nq, Lq] and the number of questions per sample (None: one each), from question_ids / question_mask
+    (+ num_questions) or raw_questions - a list of str, or for evaluation a list of lists of str (vast.py:562-573)."""
+    if "question_ids" in batch:
+        nq = batch.get("num_questions")
+        return batch["question_ids"], batch["question_mask"], None if nq is None else [int(n) for n in nq]
+    raw, nq = batch["raw_questions"], None
+    if any(isinstance(q, (list, tuple)) for q in raw):
+        nq = [len(q) for q in raw]
+        raw = [q for qs in raw for q in qs]
+    dev = self.contra_temp.device
+    tok = self.multimodal_encoder.tokenizer(list(raw), padding="max_length", truncation=True, max_length=self.max_caption_len,
+                                            return_tensors="pt")
+    return tok.input_ids.to(dev), tok.attention_mask.to(dev), nq
+
+
+def _qa_inputs(self, batch, q_ids, q_mask):
+    """[question | masked answer] ids, the answer part's labels [b, La] (TokenMasker at 0.99 or the injected draw) and the part-causal mask of the
+    QA pass (vast.py:580-599).  The labels of the question part are all -100 and are not materialised: only answer rows reach the LM head."""
+    if "answer_ids" in batch:
+        a_ids, a_mask = batch["answer_ids"], batch["answer_mask"]
+    else:
+        tok = self.multimodal_encoder.tokenizer(list(batch["raw_answers"]), padding="max_length", truncation=True,
+                                                max_length=self.max_answer_len, return_tensors="pt")
+        a_ids, a_mask = tok.input_ids.to(q_ids.device), tok.attention_mask.to(q_ids.device)
+    if a_ids.shape[0] != q_ids.shape[0]:
+        raise ValueError(f"forward_qa: {q_ids.shape[0]} questions for {a_ids.shape[0]} answers (training takes one question per sample)")
+    inj = batch.get("_injected", {})
+    if "qa" in inj:
+        masked_ids, labels = inj["qa"]["masked_ids"].to(q_ids.device), inj["qa"]["labels"].to(q_ids.device)
+    else:
+        masked_ids, labels = self.text_masker(a_ids, 0.99)
+    return torch.cat((q_ids, masked_ids), dim=1), labels, qa_attention_mask(q_mask, a_mask)
+
+
+def forward_qa(self, batch, task, compute_loss=True):
+    """Visual question answering, task strings "qa%tv", "qa%tva%tv", ... (vast.py:557-650).
+    compute_loss=True: {"loss_qa"} - per sub-task one pass over [question | answer masked at 0.99] under qa_attention_mask with the sub-task's
+    condition tokens, the masked-token loss over the ANSWER rows (the question's labels are all -100: its rows contribute neither to the value
+    nor to a gradient, so they skip the 768 x 30522 head); the mean over sub-tasks.  Like a captioning sub-task without a retrieval twin the
+    pass projects its own cross-attention K/V.  No staged (backward_scale) form.
+    compute_loss=False: {"generated_answers_<st>": list[str]}, flat in question order - beam search (beam_size, max_answer_len new tokens,
+    eos [SEP], length penalty 1) from the prompt [question | [CLS]].  A sample may carry any number of questions (raw_questions as a list of
+    lists, or num_questions); config decode_use_cache: the cached decode, each sample's condition tokens projected once and shared by its
+    questions' rows (BertForMaskedLM.generate(rows_per_condition=...)), otherwise one copy of them per question as the reference makes."""
+    batch = dict(batch) if not isinstance(batch, dict) else batch
+    kind, *subtasks = task.split("%")
+    if kind != "qa" or not subtasks:
+        raise ValueError(f"forward_qa: task {task!r} is not of the form qa%<sub-task>%...")
+    for st in subtasks:
+        assert st in SUBTASKS, st
+    enc = encode_batch(self, batch)
+    q_ids, q_mask, num_questions = _qa_questions(self, batch)
+    me = self.multimodal_encoder
+    Lq = q_ids.shape[1]
+    if compute_loss:
+        if num_questions is not None and any(n != 1 for n in num_questions):
+            raise ValueError("forward_qa: several questions per sample are an evaluation input (compute_loss=False)")
+        input_ids, labels, m3 = _qa_inputs(self, batch, q_ids, q_mask)
+        losses = []
+        for st in subtasks:
+            cond = _condition_feats(self, enc, st[1:])
+            seq = me.bert(input_ids=input_ids, attention_mask=m3, encoder_hidden_states=cond).last_hidden_state
+            losses.append(Fn.LMHeadLossFn.apply(seq[:, Lq:], labels, *me._head_params()))
+        return {"loss_qa": sum(losses) / len(losses)}
+    tk = me.tokenizer
+    nq = q_ids.shape[0]
+    out = {}
+    cached = bool(self.config.get("decode_use_cache", False))
+    prompt = torch.cat((q_ids, torch.full((nq, 1), tk.bos_token_id, dtype=torch.long, device=q_ids.device)), dim=1)
+    mask = me.update_attention_mask(q_mask.unsqueeze(1).expand(-1, Lq, -1).contiguous())       # vast.py:618-623
+    for st in subtasks:
+        cond = _condition_feats(self, enc, st[1:])
+        rows = [1] * cond.shape[0] if num_questions is None else num_questions
+        if nq == 0:
+            out[f"generated_answers_{st}"] = []
+            continue
+        ids = me.generate(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=self.max_answer_len,
+                          num_beams=self.beam_size, eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, length_penalty=1.0,
+                          use_cache=cached, rows_per_condition=rows)
+        out[f"generated_answers_{st}"] = tk.batch_decode(ids[:, Lq + 1:], skip_special_tokens=True)
+    return out
+
+
 class _StagedLoss(torch.autograd.Function):
     """The hand-over of a staged step (forward(backward_scale=...)): `value` is a loss that has ALREADY been differentiated through BERT inside
     forward, `grads[i]` = d(scale * sum of the staged losses) / d(tensors[i]) for the tower-side tensors the BERT passes read (the per-modality
@@ -261,7 +360,7 @@ def _forward_staged(self, batch, task, enc, scale):
         elif t.startswith("cap"):
             cap_sub += subtasks
         else:
-            raise NotImplementedError(t)
+            raise NotImplementedError(_UNKNOWN_FAMILY.format(t))
     cap_in = _cap_inputs(self, batch) if cap_sub else None
     keys = []
     for st in ret_sub + cap_sub:
@@ -313,7 +412,8 @@ def _forward_staged(self, batch, task, enc, scale):
 
 
 def forward(self, batch, task, compute_loss=True, backward_scale=None):
-    """Returns {"loss_itc", "loss_itm", "loss_cap"} for task strings like "ret%tva%tv_cap%tva" (vast.py:317-348).
+    """Returns {"loss_itc", "loss_itm", "loss_cap"} for task strings like "ret%tva%tv_cap%tva" (vast.py:317-348).  The question-answering
+    family ("qa%...") is not routed here - it raises NotImplementedError; call forward_qa.
     backward_scale (float; None = the direct form): staged differentiation, see _forward_staged - the factor the caller multiplies the summed
     losses with before its single backward() (1.0, or GradScaler.get_scale())."""
     batch = dict(batch) if not isinstance(batch, dict) else batch
@@ -382,5 +482,5 @@ def forward(self, batch, task, compute_loss=True, backward_scale=None):
                                                            pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=cached)
                     out[f"generated_captions_{st}"] = tk.batch_decode(ids[:, 1:], skip_special_tokens=True)
         else:
-            raise NotImplementedError(t)
+            raise NotImplementedError(_UNKNOWN_FAMILY.format(t))
     return out

@@ -399,6 +399,42 @@ def attn_decode(q, k, v, o, *, sets, rows_per_set, q_per_row, H, Sk, hd, scale, 
           "mico_attn_decode")
 
 
+def decode_set_row0(rows_per_set):
+    """The first-row table of mico_attn_decode_ragged for sets of rows_per_set[s] rows: host int32 [sets + 1], [0, r0, r0 + r1, ...]."""
+    rows = [int(r) for r in rows_per_set]
+    if not rows or min(rows) < 0:
+        raise ValueError(f"rows per set {rows}: a non-empty sequence of non-negative ints")
+    return torch.tensor([0] + rows, dtype=torch.int64).cumsum(0).to(torch.int32)
+
+
+def attn_decode_ragged(q, k, v, o, *, set_row0, rows, max_rows_per_set, q_per_row, H, Sk, hd, scale, q_rs, kv_strides, o_rs, mask=None,
+                       mask_strides=(0, 0), splits=None):
+    """attn_decode for sets that own different numbers of rows (mico_attn_decode_ragged): set s owns the query rows
+    [set_row0[s], set_row0[s + 1]) - set_row0 a DEVICE int32 [sets + 1] tensor (decode_set_row0) the caller vouches for: ascending from 0 to
+    `rows`, no set larger than max_rows_per_set.  q / o / mask rows are addressed by the global row, as in attn_decode.
+    splits: key split (None: attn_decode_splits at the largest set's query count)."""
+    if hd != 64:
+        raise MicoHipError(f"attn_decode_ragged: head size {hd} is not supported (hd 64 only)")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype or o.dtype != q.dtype:
+        raise MicoHipError("attn_decode_ragged: q / k / v / o must share one 16-bit dtype")
+    if mask is not None and mask.dtype != torch.float32:
+        raise MicoHipError("attn_decode_ragged: the mask is fp32 additive")
+    if set_row0.dtype != torch.int32 or set_row0.dim() != 1 or set_row0.numel() < 2 or not set_row0.is_contiguous() \
+            or set_row0.device != q.device:
+        raise MicoHipError("attn_decode_ragged: set_row0 is a contiguous int32 [sets + 1] tensor on the queries' device")
+    sets = set_row0.numel() - 1
+    splits = attn_decode_splits(sets, H, max_rows_per_set * q_per_row, Sk) if splits is None else int(splits)
+    l = _lib.lib()
+    nbytes = l.mico_attn_decode_ragged_ws_bytes(sets, H, max_rows_per_set, q_per_row, Sk, splits)
+    if nbytes < 0:
+        raise MicoHipError(f"attn_decode_ragged: bad shape (sets {sets}, H {H}, rows per set <= {max_rows_per_set}, q_per_row {q_per_row}, "
+                           f"Sk {Sk}, splits {splits})")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    check(l.mico_attn_decode_ragged(_p(q), q_rs, _p(k), _p(v), kv_strides[0], kv_strides[1], _p(o), o_rs, _p(mask), mask_strides[0],
+                                    mask_strides[1], sets, _p(set_row0), rows, max_rows_per_set, q_per_row, H, Sk, hd, scale, splits,
+                                    _p(ws), nbytes, dt_code(q.dtype), _st()), "mico_attn_decode_ragged")
+
+
 def decode_kv_append(src, cache, *, rows, n_new, pos0):
     """cache [rows, max_len, width] (row stride per position) <- src rows r n_new + i at positions pos0 + i (16-bit, src [rows n_new, >= width])."""
     width = cache.shape[-1]

@@ -2403,13 +2403,9 @@ class BertDecodeCache:
         def cross_attn(li, q):
             cc = _empty((N, D), dt, dev)
             kvl = self.kvx[:, li * 2 * D:]
-            # the rows_per_set x n queries of a condition set share its keys
-            if self.set_row0 is not None:
-                ops.attn_decode_ragged(q, kvl, kvl[:, D:], cc, set_row0=self.set_row0, rows=rows, max_rows_per_set=self.R, q_per_row=n, H=H,
-                                       Sk=self.E, hd=hd, scale=scale, q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
-                return cc, None
+            # the rows_per_set x n queries of a condition set share its keys (ragged sets: R is the largest, set_row0 says which rows are whose)
             ops.attn_decode(q, kvl, kvl[:, D:], cc, sets=self.sets, rows_per_set=self.R, q_per_row=n, H=H, Sk=self.E, hd=hd, scale=scale,
-                            q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D)
+                            q_rs=D, kv_strides=(self.E * kvl.stride(0), kvl.stride(0)), o_rs=D, set_row0=self.set_row0, rows=rows)
             return cc, None
 
         x32 = _bert_layers(spec, P, x32, x16, qkv_bias=self.bqkv.__getitem__, self_attn=self_attn,

@@ -295,6 +295,18 @@ class BertForMaskedLM(nn.Module):
         spec, params = self.bert._bert_spec()
         return Fn.BertDecodeCache(spec, params, self._head_params(), cond, rows_per_set, mask, self.tokenizer.mask_token_id)
 
+    def _model_step(self, input_ids, attention_mask, cond, rows_per_set, max_length, use_cache):
+        """The model step of a decode, an object with next_token_logits(ids, parent=None): the cached one (_decode_cache), or the
+        recomputing one over one copy of the condition tokens per row (arguments as _decode_cache's)."""
+        if use_cache:
+            return self._decode_cache(input_ids, attention_mask, cond, rows_per_set, max_length)
+        if cond is not None and not isinstance(rows_per_set, int):     # (the row -> set index is built on the host: no device-side size query)
+            own = torch.arange(len(rows_per_set)).repeat_interleave(torch.tensor(rows_per_set))
+            cond = cond[own.to(cond.device)]
+        elif cond is not None and rows_per_set != 1:
+            cond = cond.repeat_interleave(rows_per_set, dim=0)
+        return _RecomputingStep(self, attention_mask, cond)
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, max_new_tokens=20, num_beams=1,
                  eos_token_id=None, pad_token_id=None, length_penalty=1.0, do_sample=False, top_k=50, sample_noise=None,
@@ -333,41 +345,26 @@ class BertForMaskedLM(nn.Module):
         if do_sample:
             if int(num_beams) != 1:
                 raise TypeError("generate(): do_sample with num_beams > 1 (beam sampling) is not used by the reference and not provided")
-            enc = encoder_hidden_states
             if nrs > 1:      # sample-major rows b * n + i (vast.py:519-536 expands the condition the same way)
                 input_ids, attention_mask = input_ids.repeat_interleave(nrs, dim=0), attention_mask.repeat_interleave(nrs, dim=0)
-                if enc is not None and not use_cache:
-                    enc = enc.repeat_interleave(nrs, dim=0)
-            return self._sample(input_ids, attention_mask, enc, max_new_tokens, int(top_k), eos_token_id,
-                                pad_token_id, sample_noise, nrs if use_cache else 0)
+            max_length = input_ids.shape[1] + int(max_new_tokens)
+            dec = self._model_step(input_ids, attention_mask, encoder_hidden_states, nrs, max_length, use_cache)
+            return self._sample(dec, input_ids, max_length, int(top_k), eos_token_id, pad_token_id, sample_noise)
         dev = input_ids.device
         B, cur = input_ids.shape
         nb = int(num_beams)
         max_length = cur + int(max_new_tokens)
         ids = input_ids.repeat_interleave(nb, dim=0)
-        mask = attention_mask.repeat_interleave(nb, dim=0)
-        dec = self._decode_cache(ids, mask, encoder_hidden_states, nb if rpc is None else [r * nb for r in rpc], max_length) if use_cache else None
-        enc = None
-        if encoder_hidden_states is not None and dec is None:
-            if rpc is None:
-                enc = encoder_hidden_states.repeat_interleave(nb, dim=0).contiguous()
-            else:    # (the row -> set index is built on the host: no device-side size query)
-                own = torch.arange(len(rpc)).repeat_interleave(torch.tensor(rpc) * nb)
-                enc = encoder_hidden_states[own.to(dev)].contiguous()
+        dec = self._model_step(ids, attention_mask.repeat_interleave(nb, dim=0), encoder_hidden_states,
+                               nb if rpc is None else [r * nb for r in rpc], max_length, use_cache)
         beam_scores = torch.zeros(B, nb, dtype=torch.float32, device=dev)
         beam_scores[:, 1:] = -1e9
         beam_scores = beam_scores.view(-1)
         hyps = [_BeamHypotheses(nb, length_penalty) for _ in range(B)]
         done = [False] * B
-        # every beam of a sample attends to the same condition tokens and beams are only ever reordered within their sample, so
-        # the per-layer cross-attention K/V of `enc` are step-invariant: projected at the first step, reused afterwards
-        kv_cache = {} if enc is not None else None
         parent = None
         while True:
-            if dec is not None:
-                logits = dec.next_token_logits(ids, parent).float()
-            else:
-                logits = self.next_token_logits(ids, mask, enc, kv_cache).float()
+            logits = dec.next_token_logits(ids, parent).float()
             scores = torch.log_softmax(logits, dim=-1) + beam_scores[:, None]
             V = scores.shape[-1]
             top_s, top_i = torch.topk(scores.view(B, nb * V), 2 * nb, dim=1, largest=True, sorted=True)
@@ -398,8 +395,6 @@ class BertForMaskedLM(nn.Module):
             beam_scores = nxt_s.view(-1).to(dev)
             parent = nxt_b.view(-1)
             ids = torch.cat([ids[parent.to(dev)], nxt_t.view(-1, 1).to(dev)], dim=1)
-            if dec is None:
-                mask = self.update_attention_mask(mask)
             if all(done) or ids.shape[1] >= max_length:
                 break
         ids_cpu, fin = ids.cpu(), beam_scores.cpu()
@@ -419,29 +414,19 @@ class BertForMaskedLM(nn.Module):
         return out.to(dev)
 
 
-    def _sample(self, input_ids, attention_mask, enc, max_new_tokens, top_k, eos_token_id, pad_token_id, noise, cache_rows_per_set=0):
+    def _sample(self, dec, ids, max_length, top_k, eos_token_id, pad_token_id, noise):
         """Top-k sampling as the reference's captioner_mode asks transformers 4.31 for it (vast.py:526-536: do_sample=True, top_k=10,
         temperature 1): per step the top_k logits are kept (TopKLogitsWarper), softmax over them, ONE draw per row; rows that have
         produced eos emit pad from then on; stop when every row has finished or max_length is reached.  The draw is inverse-CDF over
         the kept candidates in descending-score order with one uniform number per (row, step): `noise` [rows, max_new_tokens] injects
         them (parity tests), otherwise they come from torch's generator - the same distribution as torch.multinomial, not the same
-        stream.  Device: model step + top-k; host: k candidates per row.
-        cache_rows_per_set > 0: the cached decode (BertDecodeCache) with `enc` holding one condition set per cache_rows_per_set rows."""
-        dev = input_ids.device
-        B, cur = input_ids.shape
-        max_length = cur + int(max_new_tokens)
-        ids, mask = input_ids, attention_mask
+        stream.  Device: model step (dec, of _model_step) + top-k; host: k candidates per row."""
+        dev = ids.device
+        B = ids.shape[0]
         unfinished = torch.ones(B, dtype=torch.bool)
-        dec = self._decode_cache(ids, mask, enc, cache_rows_per_set, max_length) if cache_rows_per_set else None
-        kv_cache = {} if enc is not None and dec is None else None
-        if enc is not None:
-            enc = enc.contiguous()
         step = 0
         while True:
-            if dec is not None:
-                logits = dec.next_token_logits(ids).float()
-            else:
-                logits = self.next_token_logits(ids, mask, enc, kv_cache).float()
+            logits = dec.next_token_logits(ids).float()
             top_s, top_i = torch.topk(logits, min(top_k, logits.shape[-1]), dim=-1, largest=True, sorted=True)
             probs = torch.softmax(top_s, dim=-1).cpu().double()
             top_i = top_i.cpu()
@@ -453,12 +438,28 @@ class BertForMaskedLM(nn.Module):
                 tok = torch.where(unfinished, tok, torch.full_like(tok, pad_token_id if pad_token_id is not None else 0))
                 unfinished = unfinished & (tok != eos_token_id)
             ids = torch.cat([ids, tok.view(-1, 1).to(dev)], dim=1)
-            if dec is None:
-                mask = self.update_attention_mask(mask)
             step += 1
             if not bool(unfinished.any()) or ids.shape[1] >= max_length:
                 break
         return ids
+
+
+class _RecomputingStep:
+    """The recomputing model step behind functional.BertDecodeCache's interface: every call runs all positions of ids plus the appended
+    [MASK] (BertForMaskedLM.next_token_logits).  Owns the 3-D mask, grown by one position per generated token."""
+
+    def __init__(self, model, attention_mask, enc):
+        self.model, self.mask = model, attention_mask
+        self.enc = enc.contiguous() if enc is not None else None
+        # a row attends to the same condition tokens at every step and rows are only ever reordered within their condition set (beams), so
+        # the per-layer cross-attention K/V of `enc` are step-invariant: projected at the first step, reused afterwards
+        self.kv_cache = {} if enc is not None else None
+
+    def next_token_logits(self, ids, parent=None):
+        """parent: not needed - nothing here is kept per row (beams are reordered within their prompt row, whose mask they share)."""
+        if self.mask.shape[1] < ids.shape[1]:
+            self.mask = self.model.update_attention_mask(self.mask)
+        return self.model.next_token_logits(ids, self.mask, self.enc, self.kv_cache)
 
 
 class _BeamHypotheses:

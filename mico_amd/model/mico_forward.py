@@ -263,6 +263,25 @@ def _qa_inputs(self, batch, q_ids, q_mask):
     return torch.cat((q_ids, masked_ids), dim=1), labels, qa_attention_mask(q_mask, a_mask)
 
 
+def _generate_text(self, cond, max_new_tokens, prefix=None, **search):
+    """Decoded continuations of the prompt [prefix | [CLS]] under the condition tokens `cond`: BertForMaskedLM.generate (eos [SEP]; `search`:
+    its beam-search or sampling arguments; config decode_use_cache: the cached decode), then the tokenizer over the new ids.
+    prefix: (ids [rows, L], mask [rows, L]) or None - one prompt row [CLS] per condition set."""
+    me = self.multimodal_encoder
+    tk = me.tokenizer
+    if prefix is None:
+        prompt = torch.full((cond.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=cond.device)
+        mask = prompt.new_ones(cond.shape[0], 1, 1)
+    else:
+        ids, m = prefix
+        prompt = torch.cat((ids, torch.full((ids.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=ids.device)), dim=1)
+        mask = me.update_attention_mask(m.unsqueeze(1).expand(-1, ids.shape[1], -1).contiguous())       # vast.py:618-623
+    out = me.generate(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=max_new_tokens,
+                      eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=bool(self.config.get("decode_use_cache", False)),
+                      **search)
+    return tk.batch_decode(out[:, prompt.shape[1]:], skip_special_tokens=True)
+
+
 def forward_qa(self, batch, task, compute_loss=True):
     """Visual question answering, task strings "qa%tv", "qa%tva%tv", ... (vast.py:557-650).
     compute_loss=True: {"loss_qa"} - per sub-task one pass over [question | answer masked at 0.99] under qa_attention_mask with the sub-task's
@@ -293,22 +312,15 @@ def forward_qa(self, batch, task, compute_loss=True):
             seq = me.bert(input_ids=input_ids, attention_mask=m3, encoder_hidden_states=cond).last_hidden_state
             losses.append(Fn.LMHeadLossFn.apply(seq[:, Lq:], labels, *me._head_params()))
         return {"loss_qa": sum(losses) / len(losses)}
-    tk = me.tokenizer
-    nq = q_ids.shape[0]
     out = {}
-    cached = bool(self.config.get("decode_use_cache", False))
-    prompt = torch.cat((q_ids, torch.full((nq, 1), tk.bos_token_id, dtype=torch.long, device=q_ids.device)), dim=1)
-    mask = me.update_attention_mask(q_mask.unsqueeze(1).expand(-1, Lq, -1).contiguous())       # vast.py:618-623
     for st in subtasks:
         cond = _condition_feats(self, enc, st[1:])
         rows = [1] * cond.shape[0] if num_questions is None else num_questions
-        if nq == 0:
+        if q_ids.shape[0] == 0:
             out[f"generated_answers_{st}"] = []
             continue
-        ids = me.generate(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=self.max_answer_len,
-                          num_beams=self.beam_size, eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, length_penalty=1.0,
-                          use_cache=cached, rows_per_condition=rows)
-        out[f"generated_answers_{st}"] = tk.batch_decode(ids[:, Lq + 1:], skip_special_tokens=True)
+        out[f"generated_answers_{st}"] = _generate_text(self, cond, self.max_answer_len, prefix=(q_ids, q_mask), num_beams=self.beam_size,
+                                                        length_penalty=1.0, rows_per_condition=rows)
     return out
 
 
@@ -452,35 +464,23 @@ def forward(self, batch, task, compute_loss=True, backward_scale=None):
                 out.update(_forward_cap(self, batch, enc, subtasks))
                 runtime.mem_trace("after forward_cap")
             else:   # evaluation dict of vast.py:513-547: beam-search captions per sub-task (captioner_mode sampling is not provided)
-                tk = self.multimodal_encoder.tokenizer
-                # decode_use_cache: incremental decoding (BertForMaskedLM.generate(use_cache=True)); the rows of a sample share its
+                # config decode_use_cache: incremental decoding (BertForMaskedLM.generate(use_cache=True)); the rows of a sample share its
                 # condition tokens' cross-attention K/V instead of a copy each
-                cached = bool(self.config.get("decode_use_cache", False))
                 for st in subtasks:
                     cond = _condition_feats(self, enc, st[1:])
                     if self.config.get("captioner_mode", False):
                         # vast.py:519-536: generate_nums sampled captions per sample (top-k 10 sampling), rows sample-major
                         gn = int(self.config.generate_nums)
                         nrs = 1
-                        if cached:
+                        if self.config.get("decode_use_cache", False):
                             nrs = gn
                         else:
                             cond = cond.unsqueeze(1).expand(-1, gn, -1, -1).reshape(-1, *cond.shape[1:]).contiguous()
-                        init = torch.full((cond.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=cond.device)
-                        ids = self.multimodal_encoder.generate(input_ids=init, attention_mask=init.new_ones(cond.shape[0], 1, 1),
-                                                               do_sample=True, top_k=10, encoder_hidden_states=cond,
-                                                               max_new_tokens=self.max_caption_len, eos_token_id=tk.sep_token_id,
-                                                               pad_token_id=tk.pad_token_id,
-                                                               sample_noise=(batch.get("_injected") or {}).get("sample_noise"),
-                                                               use_cache=cached, num_return_sequences=nrs)
-                        out[f"generated_captions_{st}"] = tk.batch_decode(ids[:, 1:], skip_special_tokens=True)
-                        continue
-                    init = torch.full((cond.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=cond.device)
-                    ids = self.multimodal_encoder.generate(input_ids=init, attention_mask=init.new_ones(cond.shape[0], 1, 1),
-                                                           encoder_hidden_states=cond, max_new_tokens=self.max_caption_len,
-                                                           num_beams=self.beam_size, eos_token_id=tk.sep_token_id,
-                                                           pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=cached)
-                    out[f"generated_captions_{st}"] = tk.batch_decode(ids[:, 1:], skip_special_tokens=True)
+                        search = dict(do_sample=True, top_k=10, sample_noise=(batch.get("_injected") or {}).get("sample_noise"),
+                                      num_return_sequences=nrs)
+                    else:
+                        search = dict(num_beams=self.beam_size, length_penalty=0.6)
+                    out[f"generated_captions_{st}"] = _generate_text(self, cond, self.max_caption_len, **search)
         else:
             raise NotImplementedError(_UNKNOWN_FAMILY.format(t))
     return out

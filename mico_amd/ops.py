@@ -376,27 +376,38 @@ def attn_decode_splits(sets, H, QR, Sk):
 
 
 def attn_decode(q, k, v, o, *, sets, rows_per_set, q_per_row, H, Sk, hd, scale, q_rs, kv_strides, o_rs, mask=None, mask_strides=(0, 0),
-                splits=None):
+                splits=None, set_row0=None, rows=None):
     """Grouped-query decode attention (mico_attn_decode): `sets` key sets of Sk keys, each read by rows_per_set x q_per_row queries.
     q / o: 16-bit, query (s, r, i) at row (s rows_per_set + r) q_per_row + i (row strides q_rs / o_rs, head h at columns h hd ..);
     k / v: key n of set s at s kv_strides[0] + n kv_strides[1]; mask: fp32 additive, row of query (s, r, i) at
-    (s rows_per_set + r) mask_strides[0] + i mask_strides[1].  splits: key split (None: attn_decode_splits)."""
+    (s rows_per_set + r) mask_strides[0] + i mask_strides[1].  splits: key split (None: attn_decode_splits).
+    set_row0 (mico_attn_decode_ragged): the sets own different numbers of rows - set s owns the query rows [set_row0[s], set_row0[s + 1]),
+    set_row0 a DEVICE int32 [sets + 1] tensor (decode_set_row0) the caller vouches for: ascending from 0 to `rows`, no set larger than
+    rows_per_set, which is then the LARGEST set's row count (it sizes the launch and the default key split).  q / o / mask rows are
+    addressed by the global row."""
     if hd != 64:
         raise MicoHipError(f"attn_decode: head size {hd} is not supported (hd 64 only)")
     if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype or o.dtype != q.dtype:
         raise MicoHipError("attn_decode: q / k / v / o must share one 16-bit dtype")
     if mask is not None and mask.dtype != torch.float32:
         raise MicoHipError("attn_decode: the mask is fp32 additive")
+    if set_row0 is not None and (set_row0.dtype != torch.int32 or set_row0.dim() != 1 or set_row0.numel() != sets + 1
+                                 or not set_row0.is_contiguous() or set_row0.device != q.device):
+        raise MicoHipError("attn_decode: set_row0 is a contiguous int32 [sets + 1] tensor on the queries' device")
     QR = rows_per_set * q_per_row
     splits = attn_decode_splits(sets, H, QR, Sk) if splits is None else int(splits)
     l = _lib.lib()
-    nbytes = l.mico_attn_decode_ws_bytes(sets, H, QR, Sk, splits)
+    nbytes = l.mico_attn_decode_ws_bytes(sets, H, QR, Sk, splits) if QR <= 0x7fffffff else -1
     if nbytes < 0:
-        raise MicoHipError(f"attn_decode: bad shape (sets {sets}, H {H}, queries {QR}, Sk {Sk}, splits {splits})")
+        raise MicoHipError(f"attn_decode: bad shape (sets {sets}, H {H}, rows per set <= {rows_per_set}, q_per_row {q_per_row}, Sk {Sk}, "
+                           f"splits {splits})")
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
-    check(l.mico_attn_decode(_p(q), q_rs, _p(k), _p(v), kv_strides[0], kv_strides[1], _p(o), o_rs, _p(mask), mask_strides[0], mask_strides[1],
-                             sets, rows_per_set, q_per_row, H, Sk, hd, scale, splits, _p(ws), nbytes, dt_code(q.dtype), _st()),
-          "mico_attn_decode")
+    head = (_p(q), q_rs, _p(k), _p(v), kv_strides[0], kv_strides[1], _p(o), o_rs, _p(mask), mask_strides[0], mask_strides[1], sets)
+    tail = (q_per_row, H, Sk, hd, scale, splits, _p(ws), nbytes, dt_code(q.dtype), _st())
+    if set_row0 is None:
+        check(l.mico_attn_decode(*head, rows_per_set, *tail), "mico_attn_decode")
+    else:
+        check(l.mico_attn_decode_ragged(*head, _p(set_row0), rows, rows_per_set, *tail), "mico_attn_decode_ragged")
 
 
 def decode_set_row0(rows_per_set):
@@ -409,30 +420,9 @@ def decode_set_row0(rows_per_set):
 
 def attn_decode_ragged(q, k, v, o, *, set_row0, rows, max_rows_per_set, q_per_row, H, Sk, hd, scale, q_rs, kv_strides, o_rs, mask=None,
                        mask_strides=(0, 0), splits=None):
-    """attn_decode for sets that own different numbers of rows (mico_attn_decode_ragged): set s owns the query rows
-    [set_row0[s], set_row0[s + 1]) - set_row0 a DEVICE int32 [sets + 1] tensor (decode_set_row0) the caller vouches for: ascending from 0 to
-    `rows`, no set larger than max_rows_per_set.  q / o / mask rows are addressed by the global row, as in attn_decode.
-    splits: key split (None: attn_decode_splits at the largest set's query count)."""
-    if hd != 64:
-        raise MicoHipError(f"attn_decode_ragged: head size {hd} is not supported (hd 64 only)")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype or o.dtype != q.dtype:
-        raise MicoHipError("attn_decode_ragged: q / k / v / o must share one 16-bit dtype")
-    if mask is not None and mask.dtype != torch.float32:
-        raise MicoHipError("attn_decode_ragged: the mask is fp32 additive")
-    if set_row0.dtype != torch.int32 or set_row0.dim() != 1 or set_row0.numel() < 2 or not set_row0.is_contiguous() \
-            or set_row0.device != q.device:
-        raise MicoHipError("attn_decode_ragged: set_row0 is a contiguous int32 [sets + 1] tensor on the queries' device")
-    sets = set_row0.numel() - 1
-    splits = attn_decode_splits(sets, H, max_rows_per_set * q_per_row, Sk) if splits is None else int(splits)
-    l = _lib.lib()
-    nbytes = l.mico_attn_decode_ragged_ws_bytes(sets, H, max_rows_per_set, q_per_row, Sk, splits)
-    if nbytes < 0:
-        raise MicoHipError(f"attn_decode_ragged: bad shape (sets {sets}, H {H}, rows per set <= {max_rows_per_set}, q_per_row {q_per_row}, "
-                           f"Sk {Sk}, splits {splits})")
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
-    check(l.mico_attn_decode_ragged(_p(q), q_rs, _p(k), _p(v), kv_strides[0], kv_strides[1], _p(o), o_rs, _p(mask), mask_strides[0],
-                                    mask_strides[1], sets, _p(set_row0), rows, max_rows_per_set, q_per_row, H, Sk, hd, scale, splits,
-                                    _p(ws), nbytes, dt_code(q.dtype), _st()), "mico_attn_decode_ragged")
+    """attn_decode(set_row0=...) under the library entry point's argument names: sets = set_row0.numel() - 1, `rows` query rows in all."""
+    attn_decode(q, k, v, o, sets=set_row0.numel() - 1, rows_per_set=max_rows_per_set, q_per_row=q_per_row, H=H, Sk=Sk, hd=hd, scale=scale,
+                q_rs=q_rs, kv_strides=kv_strides, o_rs=o_rs, mask=mask, mask_strides=mask_strides, splits=splits, set_row0=set_row0, rows=rows)
 
 
 def decode_kv_append(src, cache, *, rows, n_new, pos0):

@@ -69,34 +69,48 @@ def _ref_set(q, kv_s, mask, Sk, H):
     return (torch.softmax(s, -1) @ v).permute(1, 0, 2).reshape(-1, D)
 
 
+def _check_ragged(dev, dtype, rows_per_set, Qp, Sk, H, splits, masked, seed):
+    """fp32 torch attention within the uniform kernel's bound, every set bit-identical to the uniform launch over that set alone, a repeated
+    launch bit-identical, rows that belong to no set untouched"""
+    tag = (Qp, masked)
+    q, kv, mask = _case(dev, dtype, rows_per_set, Qp, Sk, H, masked, seed=seed)
+    o = _ragged(q, kv, mask, rows_per_set, Qp, Sk, H, splits, tail_rows=4)
+    n = q.shape[0]
+    assert bool((o[n:] == SENTINEL).all()), tag                 # only owned rows change
+    assert torch.equal(o, _ragged(q, kv, mask, rows_per_set, Qp, Sk, H, splits, tail_rows=4)), tag
+    r0 = 0
+    for s, R in enumerate(rows_per_set):
+        if R == 0:
+            continue
+        sl = slice(r0 * Qp, (r0 + R) * Qp)
+        ms = mask[r0:r0 + R] if masked else None
+        ref = _ref_set(q[sl], kv[s], ms.reshape(R * Qp, Sk) if masked else None, Sk, H)
+        err = ((o[sl].float() - ref).abs().max() / ref.abs().max()).item()
+        assert err < tol(dtype, 1.5), (tag, s, err)
+        alone = _uniform(q[sl], kv[s:s + 1], ms, 1, R, Qp, Sk, H, splits)
+        assert torch.equal(o[sl], alone), (tag, s)
+        r0 += R
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("rows_per_set", [(1, 5, 2), (3, 0, 4)])
 @pytest.mark.parametrize("Sk,splits", [(70, 1), (197, 2), (197, 3)])
 def test_ragged_decode_attention(cuda, dtype, rows_per_set, Sk, splits):
-    """A set smaller than one 4-query chunk, a set that ends mid-chunk, an empty set; with and without the key split and the mask: fp32 torch
-    attention within the uniform kernel's bound, every set bit-identical to the uniform launch over that set alone, a repeated launch
-    bit-identical, rows that belong to no set untouched."""
-    H = 2
+    """A set smaller than one 4-query chunk, a set that ends mid-chunk, an empty set; with and without the key split and the mask
+    (_check_ragged)."""
     for Qp in (2, 3):
         for masked in (False, True):
-            tag = (Qp, masked)
-            q, kv, mask = _case(cuda, dtype, rows_per_set, Qp, Sk, H, masked, seed=Sk + 10 * Qp + sum(rows_per_set))
-            o = _ragged(q, kv, mask, rows_per_set, Qp, Sk, H, splits, tail_rows=4)
-            n = q.shape[0]
-            assert bool((o[n:] == SENTINEL).all()), tag                 # only owned rows change
-            assert torch.equal(o, _ragged(q, kv, mask, rows_per_set, Qp, Sk, H, splits, tail_rows=4)), tag
-            r0 = 0
-            for s, R in enumerate(rows_per_set):
-                if R == 0:
-                    continue
-                sl = slice(r0 * Qp, (r0 + R) * Qp)
-                ms = mask[r0:r0 + R] if masked else None
-                ref = _ref_set(q[sl], kv[s], ms.reshape(R * Qp, Sk) if masked else None, Sk, H)
-                err = ((o[sl].float() - ref).abs().max() / ref.abs().max()).item()
-                assert err < tol(dtype, 1.5), (tag, s, err)
-                alone = _uniform(q[sl], kv[s:s + 1], ms, 1, R, Qp, Sk, H, splits)
-                assert torch.equal(o[sl], alone), (tag, s)
-                r0 += R
+            _check_ragged(cuda, dtype, rows_per_set, Qp, Sk, 2, splits, masked, seed=Sk + 10 * Qp + sum(rows_per_set))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rows_per_set", [(1, 2, 0, 1), (2,)])
+@pytest.mark.parametrize("Sk,splits", [(70, 1), (197, 3)])
+def test_ragged_decode_attention_two_query_instantiation(cuda, dtype, rows_per_set, Sk, splits):
+    """One query per row and no set larger than two rows: the launch takes the 2-query instantiation (the cases above all reach the 4-query
+    one).  Same assertions (_check_ragged)."""
+    for masked in (False, True):
+        _check_ragged(cuda, dtype, rows_per_set, 1, Sk, 2, splits, masked, seed=Sk + sum(rows_per_set))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

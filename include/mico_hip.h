@@ -491,6 +491,23 @@ int mico_ce_fwd_bwd(const void* logits, int logits_dtype, int64_t ld, int64_t ro
                     float* row_loss, float* row_lse,
                     void* dlogits, int dlogits_dtype, int64_t ld_d, const float* dscale_ptr, float dscale,
                     int dtype, void* stream);
+/* Per-row log-probabilities with per-row upstream gradients (ABI 119; functional.LMHeadLogProbFn - scoring a sampled caption, SCST): the
+ * schedule of mico_ce_fwd_bwd, whose kernel it instantiates with a gradient scale per row.  logits: fp32 or 16-bit [rows, cols] (ld).
+ *   row_logp[r] (fp32, may be NULL) = logits[r, target[r]] - logsumexp(logits[r, :cols]);  0 where target[r] == ignore_index (or out of range)
+ *   dlogits (may be NULL; the logits' dtype, row stride ld_d, may alias logits) [r, :] = gscale * row_gscale[r] * (onehot(target[r]) - softmax);
+ *   a zero row where the target is ignored.  row_gscale: fp32 [rows], required with dlogits. */
+int mico_logprob_fwd_bwd(const void* logits, int logits_dtype, int64_t ld, int64_t rows, int cols, const int64_t* target, int ignore_index,
+                         float* row_logp, void* dlogits, int64_t ld_d, const float* row_gscale, float gscale, void* stream);
+/* One draw per row from softmax(logits[r, :cols]) over the full vocabulary (ABI 119; generate(do_sample=True, top_k=0), generate_scst).
+ * logits: fp32 [rows, cols] (ld), finite or -inf; u: fp32 [rows] uniform numbers in [0, 1) supplied by the caller.  Inverse-CDF in column
+ * order by mico_itm_sample's rule: token[r] = the first column whose running sum of e^(x - max) exceeds u[r] * total, `total` being that
+ * running sum's own last value; a column of zero weight (-inf, or underflowed) is never drawn, and when rounding puts the target at or past
+ * the total the answer is the last column with a weight.  logp[r] = logits[r, token] - (max + log total).  unfinished (may be NULL):
+ * one byte per row, in / out - a row whose byte is 0 emits pad_id with logp 0 and stays 0; a row that draws eos_id (pass -1 for none) gets
+ * its byte cleared.  token: int64 [rows].  One 256-thread workgroup per row, no host synchronisation, the same result for the same inputs.
+ * A row without any finite logit has no distribution: token 0, logp -inf. */
+int mico_vocab_sample(const float* logits, int64_t ld, int rows, int cols, const float* u, unsigned char* unfinished, int eos_id, int pad_id,
+                      int64_t* token, float* logp, void* stream);
 /* Small exact-fp32 GEMM for the tiny heads and similarity matrices (contra heads, itm head, ITC logits; vast.py:405-408,
  * mico.py:36-52): C = alpha * opA(A) opB(B) + beta * C, same ta/tb convention as mico_gemm, any sizes, fp32 everywhere. */
 int mico_sgemm_small(int ta, int tb, int M, int N, int K, const float* A, int64_t lda, const float* B, int64_t ldb,

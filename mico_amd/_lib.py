@@ -113,6 +113,8 @@ PROTOTYPES = {
     "mico_patch_merge": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
     "mico_ce_fwd_bwd": [c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_int, c_f, c_f, c_vp, c_vp, c_vp, c_int, c_i64,
                         c_vp, c_f, c_int, c_vp],
+    "mico_logprob_fwd_bwd": [c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_f, c_vp],
+    "mico_vocab_sample": [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
     "mico_sgemm_small": [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp],
     "mico_gelu_f32": [c_vp, c_vp, c_i64, c_vp],
     "mico_gelu_bwd_f32": [c_vp, c_vp, c_vp, c_i64, c_vp],
@@ -147,7 +149,7 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 118   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 119   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):

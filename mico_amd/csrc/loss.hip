@@ -9,7 +9,9 @@ namespace {
 
 template <typename LT> __device__ __forceinline__ float ld_logit(const LT* p, int64_t i) { return (float)p[i]; }
 
-template <typename LT, typename DT>
+// LOGP (mico_logprob_fwd_bwd): row_loss receives log P(target) = x[target] - lse instead of the loss, and dscale_ptr is one upstream
+// gradient PER ROW, fp32 [rows]: dlogits = dscale * dscale_ptr[row] * (onehot - softmax).  The loss instantiation is untouched by it.
+template <typename LT, typename DT, bool LOGP = false>
 __global__ __launch_bounds__(256) void ce_kernel(const LT* __restrict__ logits, int64_t ld, int cols,
                                                  const int64_t* __restrict__ target, int ignore_index, float ls,
                                                  float lscale, float* __restrict__ row_loss, float* __restrict__ row_lse,
@@ -47,14 +49,16 @@ __global__ __launch_bounds__(256) void ce_kernel(const LT* __restrict__ logits, 
         float loss = 0.f;
         if (!ignored) {
             const float xt = ld_logit(x, t) * lscale;
-            loss = (1.f - ls) * (lse - xt) + ls * (lse - SX / (float)cols);
+            if constexpr (LOGP) loss = xt - lse;
+            else loss = (1.f - ls) * (lse - xt) + ls * (lse - SX / (float)cols);
         }
         if (row_loss) row_loss[row] = loss;
         if (row_lse) row_lse[row] = lse;
     }
     if (!dlogits) return;
     float ds = dscale * lscale;
-    if (dscale_ptr) ds *= dscale_ptr[0];
+    if constexpr (LOGP) ds *= -dscale_ptr[row];      // (softmax - onehot) below, the other sign
+    else if (dscale_ptr) ds *= dscale_ptr[0];
     if (ignored) ds = 0.f;
     const float smooth = ls / (float)cols;
     DT* d = dlogits + row * ld_d;
@@ -104,6 +108,76 @@ __global__ __launch_bounds__(64) void itm_sample_kernel(const float* __restrict_
     if (lane == 0) {
         if (cnt >= cols) cnt = (dcol == cols - 1) ? cols - 2 : cols - 1;   // u * total rounded up to the total: the last column with weight
         out[row] = max(cnt, 0);
+    }
+}
+
+// Full-vocabulary draw (mico_vocab_sample): one 256-thread workgroup per row, every thread a contiguous chunk of the row, which is read
+// three times (max; weights e^(x - max) summed per chunk; the search) - the second and third time from L2.  The running sum of column j is
+// (exclusive block scan of the chunk sums) + (the chunk's own sequential sum up to j), `total` the scan's last value.  The drawn column is
+// found as a minimum over the columns that qualify (running sum above u * total AND a non-zero weight), so a zero-weight column cannot be
+// drawn whatever the rounding at a chunk boundary does; when no column qualifies (u * total rounded up to the total) it is the last
+// column with a weight.
+__global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restrict__ logits, int64_t ld, int cols, const float* __restrict__ u,
+                                                           unsigned char* __restrict__ unfinished, int eos, int pad,
+                                                           int64_t* __restrict__ token, float* __restrict__ logp) {
+    __shared__ float redf[4];
+    __shared__ int redi[2][4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (unfinished && !unfinished[row]) {       // (block-uniform)
+        if (tid == 0) { token[row] = pad; logp[row] = 0.f; }
+        return;
+    }
+    const float* x = logits + (int64_t)row * ld;
+    const int chunk = (cols + 255) / 256;
+    const int j0 = min(cols, tid * chunk), j1 = min(cols, j0 + chunk);
+    float m = -3.0e38f;
+    for (int j = j0; j < j1; ++j) m = fmaxf(m, x[j]);
+    m = wave_max(m);
+    if (lane == 0) redf[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+    __syncthreads();
+    float part = 0.f;
+    for (int j = j0; j < j1; ++j) part += __expf(x[j] - m);
+    float incl = part;      // inclusive scan over the lanes, then over the waves
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) redf[wave] = incl;
+    __syncthreads();
+    float before = 0.f;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) before += (w < wave) ? redf[w] : 0.f;
+    const float total = ((redf[0] + redf[1]) + redf[2]) + redf[3];
+    const float tgt = u[row] * total;
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    float run = before + excl;
+    int first = cols, last = -1;
+    for (int j = j0; j < j1; ++j) {
+        const float w = __expf(x[j] - m);
+        run += w;
+        if (w > 0.f) {
+            last = j;
+            if (run > tgt && first == cols) first = j;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        first = min(first, __shfl_xor(first, d, 64));
+        last = max(last, __shfl_xor(last, d, 64));
+    }
+    if (lane == 0) { redi[0][wave] = first; redi[1][wave] = last; }
+    __syncthreads();
+    if (tid == 0) {
+        first = min(min(redi[0][0], redi[0][1]), min(redi[0][2], redi[0][3]));
+        last = max(max(redi[1][0], redi[1][1]), max(redi[1][2], redi[1][3]));
+        const int tok = first < cols ? first : max(last, 0);      // (no column with a weight at all - nothing finite in the row: column 0)
+        token[row] = tok;
+        logp[row] = last < 0 ? -INFINITY : x[tok] - (m + logf(total));
+        if (unfinished && tok == eos) unfinished[row] = 0;
     }
 }
 
@@ -301,6 +375,34 @@ extern "C" int mico_ce_fwd_bwd(const void* logits, int logits_dtype, int64_t ld,
     else if (logits_dtype == MICO_F16) CE(f16);
     else CE(bf16);
 #undef CE
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_logprob_fwd_bwd(const void* logits, int logits_dtype, int64_t ld, int64_t rows, int cols, const int64_t* target,
+                                    int ignore_index, float* row_logp, void* dlogits, int64_t ld_d, const float* row_gscale, float gscale,
+                                    void* stream) {
+    MICO_CHECK(logits && target && cols > 0 && ld >= cols, "mico_logprob_fwd_bwd: bad args");
+    MICO_CHECK(logits_dtype == MICO_F32 || logits_dtype == MICO_F16 || logits_dtype == MICO_BF16, "mico_logprob_fwd_bwd: logits dtype");
+    MICO_CHECK(!dlogits || (row_gscale && ld_d >= cols), "mico_logprob_fwd_bwd: the gradient pass needs row_gscale [rows] and ld_d >= cols");
+    if (rows <= 0) return MICO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)rows), block(256);
+#define LP(LT) MICO_LAUNCH((ce_kernel<LT, LT, true>), grid, block, 0, st, (const LT*)logits, ld, cols, target, ignore_index, 0.f, 1.f, row_logp, (float*)nullptr, (LT*)dlogits, ld_d, row_gscale, gscale)
+    if (logits_dtype == MICO_F32) LP(float);
+    else if (logits_dtype == MICO_F16) LP(f16);
+    else LP(bf16);
+#undef LP
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_vocab_sample(const float* logits, int64_t ld, int rows, int cols, const float* u, unsigned char* unfinished, int eos_id,
+                                 int pad_id, int64_t* token, float* logp, void* stream) {
+    MICO_CHECK(logits && u && token && logp && cols > 0 && ld >= cols, "mico_vocab_sample: bad args");
+    if (rows <= 0) return MICO_OK;
+    MICO_LAUNCH(vocab_sample_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, logits, ld, cols, u, unfinished, eos_id, pad_id, token,
+                logp);
     MICO_LAUNCH_CHECK();
     return MICO_OK;
 }

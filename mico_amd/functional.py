@@ -1942,17 +1942,20 @@ def _bert_layers(spec, P, x32, x16, *, qkv_bias, self_attn, cross_attn, hidden_d
 
 class BertFn(torch.autograd.Function):
     # forward's arguments in front of *params; backward finds its gradient slots and ctx.needs_input_grad entries by these names
-    ARGS = ("spec", "input_ids", "add_mask", "cond", "drop", "kv_own", "kv_neg", "kv_cache", "kv_index", "kv_sets")
+    ARGS = ("spec", "input_ids", "add_mask", "cond", "drop", "kv_own", "kv_neg", "kv_cache", "kv_index", "kv_sets", "pos_ids")
 
     @staticmethod
-    def forward(ctx, spec, input_ids, add_mask, cond, drop, kv_own, kv_neg, kv_cache, kv_index, kv_sets, *params):
+    def forward(ctx, spec, input_ids, add_mask, cond, drop, kv_own, kv_neg, kv_cache, kv_index, kv_sets, pos_ids, *params):
         """kv_own / kv_neg (CrossKVFn outputs, 2-D [n E, L * 2 D]) instead of cond: the cross-attention K/V memory is given; a batch of
         n entries reads kv_own, one of 3 n entries is the ITM triplet [own | neg | own] and reads [kv_own | kv_neg] modulo 2 n.
         drop: None (eval) or (p_hidden, p_attention, seed) - train-mode dropout of bert.py:148,267,295,373.
         kv_cache (dict or None, inference only): the per-layer cross-attention K/V projections of `cond` are stored in / taken from
         that dict, so a decode loop projects its (constant) condition tokens once instead of at every step.
         kv_index (int32 [b] or None, inference only, with the kv_own of cross_kv_memory holding kv_sets sets): batch entry i
-        attends to set kv_index[i] (mico_attn_params.kv_index) - retrieval re-ranking, where every candidate is projected once."""
+        attends to set kv_index[i] (mico_attn_params.kv_index) - retrieval re-ranking, where every candidate is projected once.
+        pos_ids (int64 [S] or None = arange(S)): the position id of every sequence position, shared by all batch entries (the two-stream
+        scoring pass).  The rows of the position table are gathered here into an [S, D] table for the embedding kernel; the backward
+        folds that table's gradient back into the parameter's rows."""
         runtime.remember_precision(ctx)
         dt = runtime.compute_dtype()
         ph, pa, dseed = drop if drop is not None else (0.0, 0.0, 0)
@@ -1966,7 +1969,11 @@ class BertFn(torch.autograd.Function):
         rows = b * S
         ids = input_ids.contiguous()
         emb = _empty((rows, D), torch.float32, dev)
-        ops.bert_embed_fwd(ids, P("embeddings.word_embeddings.weight").detach(), P("embeddings.position_embeddings.weight").detach(),
+        pos_w = P("embeddings.position_embeddings.weight").detach()
+        if pos_ids is not None:
+            assert pos_ids.shape == (S,) and pos_ids.dtype == torch.long
+            pos_w = pos_w[pos_ids].contiguous()
+        ops.bert_embed_fwd(ids, P("embeddings.word_embeddings.weight").detach(), pos_w,
                            P("embeddings.token_type_embeddings.weight").detach()[0].contiguous(), emb, S)
         split0 = runtime.split_activations()
         x32, x16 = _empty((rows, D), torch.float32, dev), _empty((rows, 2 * D if split0 else D), dt, dev)
@@ -2043,6 +2050,7 @@ class BertFn(torch.autograd.Function):
         ctx.drop = drop
         ctx.cond_needs_grad = cond is not None and cond.requires_grad
         ctx.kv_shared = (kv_own is not None, kv_neg is not None)
+        ctx.pos_ids = pos_ids
         return x32.view(b, S, D)
 
     @staticmethod
@@ -2161,7 +2169,12 @@ class BertFn(torch.autograd.Function):
         ops.layernorm_bwd(g, emb, P("embeddings.LayerNorm.weight"), mean_e, rstd_e, dx32=g,
                           dgamma=G("embeddings.LayerNorm.weight"), dbeta=G("embeddings.LayerNorm.bias"), dtype=dt)
         dtype0 = torch.zeros(D, dtype=torch.float32, device=dev)
-        ops.embed_scatter_add(ids, g, G("embeddings.word_embeddings.weight"), G("embeddings.position_embeddings.weight"), dtype0, S)
+        dpos = G("embeddings.position_embeddings.weight")
+        if ctx.pos_ids is not None:      # the gathered table's gradient [S, D], then row s of it onto row pos_ids[s] of the parameter's
+            dpos = torch.zeros((S, D), dtype=torch.float32, device=dev)
+        ops.embed_scatter_add(ids, g, G("embeddings.word_embeddings.weight"), dpos, dtype0, S)
+        if ctx.pos_ids is not None:
+            G("embeddings.position_embeddings.weight").index_add_(0, ctx.pos_ids, dpos)
         G("embeddings.token_type_embeddings.weight")[0].add_(dtype0)
         lead = dict.fromkeys(BertFn.ARGS)
         if dcond is not None and ctx.cond_needs_grad:
@@ -2206,6 +2219,34 @@ def _lm_head_fwd(seq, wt, bt, g, beta, wdec, bdec, *, for_backward, logits_dtype
     return logits, x16, pre, act, hl, mean, rstd
 
 
+def _lm_head_bwd(dlog, x16, pre, act, hl, mean, rstd, wt, g, wdec, V):
+    """The head's backward from dlog [rows, Vp], the logits' gradient times runtime.grad_scale() in their 16-bit dtype (what _lm_head_fwd kept
+    for it): (d seq rows [rows, D], d wt, d bt, d gamma, d beta, d wdec, d bdec), fp32."""
+    dt, dev = dlog.dtype, dlog.device
+    rows, D = x16.shape
+    Vp = dlog.shape[1]
+    inv_s = 1.0 / runtime.grad_scale()
+    dwdec = torch.zeros(wdec.shape, dtype=torch.float32, device=dev)
+    linear_wgrad(dlog, hl, dwdec, inv_s, n_out=V, n_in=D)
+    dbdec = torch.zeros(V, dtype=torch.float32, device=dev)
+    ops.colsum(dlog, dbdec, cols=V, scale=inv_s)
+    wd16 = runtime.gemm_weight([wdec], "wdec", n_pad=Vp)[0]
+    dhl = _empty((rows, D), dt, dev)
+    ops.gemm(dlog, wd16, dhl, tb=True, M=rows, N=D, K=Vp)
+    dact = _empty((rows, D), dt, dev)
+    dg, dbeta = torch.zeros_like(g, dtype=torch.float32), torch.zeros_like(g, dtype=torch.float32)
+    ops.layernorm_bwd(dhl, act, g.detach(), mean, rstd, dx16=dact, dgamma=dg, dbeta=dbeta, grad_scale=inv_s, dtype=dt)
+    dpre = dhl
+    ops.gelu_bwd_16(pre, dact, dpre)
+    dwt = torch.zeros(wt.shape, dtype=torch.float32, device=dev)
+    linear_wgrad(dpre, x16, dwt, inv_s)
+    dbt = torch.zeros(D, dtype=torch.float32, device=dev)
+    ops.colsum(dpre, dbt, scale=inv_s)
+    dx = _empty((rows, D), torch.float32, dev)
+    ops.gemm(dpre, _fused_w("w1", [wt]), dx, tb=True, M=rows, N=D, K=D, alpha=inv_s)
+    return dx, dwt, dbt, dg, dbeta, dwdec, dbdec
+
+
 class LMHeadLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, seq, labels, wt, bt, g, beta, wdec, bdec):
@@ -2227,10 +2268,7 @@ class LMHeadLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         x16, pre, act, hl, mean, rstd, logits, lab, n_valid, wt, g, wdec = ctx.saved_tensors
         dt, V, Vp, seq_shape = ctx.meta
-        dev = gout.device
-        rows, D = x16.shape
         S = runtime.grad_scale()
-        inv_s = 1.0 / S
         dsc = (gout.float() * S / n_valid).reshape(1).contiguous()
         if getattr(ctx, "_logits_consumed", False):
             raise RuntimeError("LMHeadLossFn: a second backward through the same graph - the 16-bit logits were overwritten by their "
@@ -2240,25 +2278,43 @@ class LMHeadLossFn(torch.autograd.Function):
         if Vp != V:
             dlog[:, V:].zero_()
         ops.ce_fwd_bwd(logits, lab, cols=V, dlogits=dlog, dscale_ptr=dsc)
-        dwdec = torch.zeros(wdec.shape, dtype=torch.float32, device=dev)
-        linear_wgrad(dlog, hl, dwdec, inv_s, n_out=V, n_in=D)
-        dbdec = torch.zeros(V, dtype=torch.float32, device=dev)
-        ops.colsum(dlog, dbdec, cols=V, scale=inv_s)
-        wd16 = runtime.gemm_weight([wdec], "wdec", n_pad=Vp)[0]
-        dhl = _empty((rows, D), dt, dev)
-        ops.gemm(dlog, wd16, dhl, tb=True, M=rows, N=D, K=Vp)
-        dact = _empty((rows, D), dt, dev)
-        dg, dbeta = torch.zeros_like(g, dtype=torch.float32), torch.zeros_like(g, dtype=torch.float32)
-        ops.layernorm_bwd(dhl, act, g.detach(), mean, rstd, dx16=dact, dgamma=dg, dbeta=dbeta, grad_scale=inv_s, dtype=dt)
-        dpre = dhl
-        ops.gelu_bwd_16(pre, dact, dpre)
-        dwt = torch.zeros(wt.shape, dtype=torch.float32, device=dev)
-        linear_wgrad(dpre, x16, dwt, inv_s)
-        dbt = torch.zeros(D, dtype=torch.float32, device=dev)
-        ops.colsum(dpre, dbt, scale=inv_s)
-        dx = _empty((rows, D), torch.float32, dev)
-        ops.gemm(dpre, _fused_w("w1", [wt]), dx, tb=True, M=rows, N=D, K=D, alpha=inv_s)
-        return dx.view(seq_shape), None, dwt, dbt, dg, dbeta, dwdec, dbdec
+        dx, *dparams = _lm_head_bwd(dlog, x16, pre, act, hl, mean, rstd, wt, g, wdec, V)
+        return (dx.view(seq_shape), None, *dparams)
+
+
+class LMHeadLogProbFn(torch.autograd.Function):
+    """log P(target) per row through the LM head, fp32 [rows] (0 where the target is -100), with LMHeadLossFn's schedule: 16-bit logits, no
+    fp32 [rows, 30522] tensor, the logits overwritten by their gradient in the backward - which takes one upstream gradient PER ROW
+    (mico_logprob_fwd_bwd), so a caller can weight every sequence differently (SCST: the advantage)."""
+
+    @staticmethod
+    def forward(ctx, seq, targets, wt, bt, g, beta, wdec, bdec):
+        runtime.remember_precision(ctx)
+        tgt = targets.reshape(-1).contiguous()
+        logits, x16, pre, act, hl, mean, rstd = _lm_head_fwd(seq, wt, bt, g, beta, wdec, bdec, for_backward=True, logits_dtype=None)
+        rows, Vp = logits.shape
+        V = wdec.shape[0]
+        logp = _empty((rows,), torch.float32, seq.device)
+        ops.logprob_fwd_bwd(logits, tgt, cols=V, row_logp=logp)
+        ctx.save_for_backward(x16, pre, act, hl, mean, rstd, logits, tgt, wt, g, wdec)
+        ctx.meta = (logits.dtype, V, Vp, seq.shape)
+        return logp.view(targets.shape)
+
+    @staticmethod
+    @runtime.saved_precision
+    def backward(ctx, gout):
+        x16, pre, act, hl, mean, rstd, logits, tgt, wt, g, wdec = ctx.saved_tensors
+        dt, V, Vp, seq_shape = ctx.meta
+        if getattr(ctx, "_logits_consumed", False):
+            raise RuntimeError("LMHeadLogProbFn: a second backward through the same graph - the 16-bit logits were overwritten by their "
+                               "gradient in the first one (no fp32 [rows, 30522] copy is kept); re-run the forward instead of retain_graph")
+        ctx._logits_consumed = True
+        dlog = logits   # overwrite the logits with their gradient (same dtype / shape)
+        if Vp != V:
+            dlog[:, V:].zero_()
+        ops.logprob_fwd_bwd(logits, tgt, cols=V, dlogits=dlog, row_gscale=gout.reshape(-1).float().contiguous(), gscale=runtime.grad_scale())
+        dx, *dparams = _lm_head_bwd(dlog, x16, pre, act, hl, mean, rstd, wt, g, wdec, V)
+        return (dx.view(seq_shape), None, *dparams)
 
 
 class LMLogitsFn(torch.autograd.Function):

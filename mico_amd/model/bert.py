@@ -10,7 +10,7 @@ import os
 import torch
 from torch import nn
 
-from .. import functional as Fn
+from .. import functional as Fn, ops
 
 BERT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                    max_position_embeddings=512, type_vocab_size=2, layer_norm_eps=1e-12, pad_token_id=0,
@@ -86,6 +86,48 @@ def extended_attention_mask(attention_mask):
     return ((1.0 - attention_mask.to(torch.float32)) * -10000.0).contiguous()
 
 
+def two_stream_inputs(input_ids, attention_mask, prompt_len, mask_token_id):
+    """The inputs of the one-pass scoring of finished sequences under the [MASK]-append protocol (BertForMaskedLM.sequence_logprobs).
+    input_ids [R, L] = a prompt of P = prompt_len positions and T = L - P generated ones; attention_mask: the prompt's {0, 1} mask
+    [R, P, P], or that mask already grown to [R, L, L] (update_attention_mask, call it G).  Returns (ids [R, S2], mask [R, S2, S2],
+    position ids [S2]) with S2 = (L - 1) + T:
+      token stream  positions 0 .. L - 2 hold the real ids under G[:, :L-1, :L-1]; they see no column of the mask stream;
+      mask stream   one [MASK] per generated position t = P .. L - 1, position id t: it sees the token columns j < t with G[t, j] = 1 and
+                    itself - not token column t, no other [MASK].
+    That is the row the [MASK] had when it was appended at step t, and since no position attends to a later one the token stream's rows are
+    what they were at every step: the T mask-stream outputs are the T steps' outputs.  Pure torch; runs on CPU tensors as well."""
+    R, L = input_ids.shape
+    P = int(prompt_len)
+    T = L - P
+    if P < 1 or T < 1:
+        raise ValueError(f"two_stream_inputs: a prompt of {P} and {T} generated positions in ids of length {L}")
+    G = attention_mask
+    if G.dim() != 3 or G.shape[0] != R or G.shape[1] != G.shape[2] or G.shape[1] not in (P, L):
+        raise ValueError(f"two_stream_inputs: attention_mask {tuple(G.shape)} is neither the prompt's [{R}, {P}, {P}] nor the grown [{R}, {L}, {L}]")
+    while G.shape[1] < L:
+        G = BertForMaskedLM.update_attention_mask(G)
+    dev = input_ids.device
+    S2 = L - 1 + T
+    ids = torch.cat((input_ids[:, :L - 1], torch.full((R, T), int(mask_token_id), dtype=input_ids.dtype, device=dev)), dim=1)
+    mask = G.new_zeros(R, S2, S2)
+    mask[:, :L - 1, :L - 1] = G[:, :L - 1, :L - 1]
+    t = torch.arange(P, L, device=dev)
+    earlier = (torch.arange(L - 1, device=dev)[None, :] < t[:, None]).to(G.dtype)           # [T, L - 1]: token column j < t
+    mask[:, L - 1:, :L - 1] = G[:, P:, :L - 1] * earlier
+    k = torch.arange(T, device=dev)
+    mask[:, L - 1 + k, L - 1 + k] = 1
+    return ids, mask, torch.cat((torch.arange(L - 1, device=dev), t))
+
+
+def first_eos_valid(tokens, eos_token_id):
+    """bool [R, T]: position t of row r is at or before the row's first eos (all True without an eos id) - the generated positions that
+    count; everything after is padding."""
+    if eos_token_id is None:
+        return torch.ones_like(tokens, dtype=torch.bool)
+    is_eos = (tokens == int(eos_token_id)).long()
+    return (is_eos.cumsum(1) - is_eos) == 0
+
+
 class BertModel(nn.Module):
     def __init__(self, c):
         super().__init__()
@@ -121,8 +163,9 @@ class BertModel(nn.Module):
         return kv_own, kv_neg
 
     def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, kv_cache=None, cross_kv=None, kv_index=None,
-                kv_sets=None, **_):
-        """kv_index (int32 [b], inference only) with cross_kv = the interleaved K/V memory of project_cross_kv under no_grad, [sets E, L 2 D]
+                kv_sets=None, position_ids=None, **_):
+        """position_ids (int64 [S], None = arange(S)): one position id per sequence position, shared by all batch entries.
+        kv_index (int32 [b], inference only) with cross_kv = the interleaved K/V memory of project_cross_kv under no_grad, [sets E, L 2 D]
         (kv_sets = sets) or viewed [sets, E, L 2 D]: batch entry i attends to set kv_index[i], so b is independent of the number of sets
         (retrieval re-ranking: every candidate projected once, read by all its pairs).  The values must lie in [0, sets).
         kv_cache (dict, inference only): holds the cross-attention K/V projections of `encoder_hidden_states` across calls -
@@ -165,8 +208,12 @@ class BertModel(nn.Module):
                 raise ValueError("cross_kv with hard negatives expects the ITM triplet batch [own | negative | own]")
         elif kv_index is not None:
             raise ValueError("kv_index needs cross_kv")
+        if position_ids is not None:
+            if position_ids.dtype != torch.long or position_ids.shape != (input_ids.shape[1],):
+                raise ValueError(f"position_ids is an int64 [{input_ids.shape[1]}] tensor, one id per sequence position")
+            position_ids = position_ids.to(input_ids.device).contiguous()
         seq = Fn.BertFn.apply(spec, input_ids, extended_attention_mask(attention_mask), encoder_hidden_states, drop, kv_own, kv_neg,
-                              kv_cache, kv_index, int(kv_sets or 0), *params)
+                              kv_cache, kv_index, int(kv_sets or 0), position_ids, *params)
         return _Out(last_hidden_state=seq)
 
 
@@ -316,6 +363,8 @@ class BertForMaskedLM(nn.Module):
         2*num_beams candidates per step, finished hypotheses scored sum_logprob / len**length_penalty, the "cannot improve"
         stop heuristic, finalisation with the open beams, eos-terminated pad-filled output.  The search bookkeeping runs on
         the host over 2*num_beams candidates per sample; the model step and log-softmax / top-k run on the device.
+        top_k = 0 (sampling): no top-k warper, as in transformers - one draw per row and step from the full softmax on the device
+        (mico_vocab_sample; _rollout), `sample_noise`, num_return_sequences and use_cache as for top-k sampling.
         use_cache: incremental decoding (functional.BertDecodeCache) - one pass over the prompt, then 2 positions per row and step;
         the rows of one condition set (beams, sampled captions) share its cross-attention K/V.  Same ids as the recomputing path up to
         floating-point reduction order.  num_return_sequences (sampling only): n rows per condition set, sample-major.
@@ -348,7 +397,11 @@ class BertForMaskedLM(nn.Module):
             if nrs > 1:      # sample-major rows b * n + i (vast.py:519-536 expands the condition the same way)
                 input_ids, attention_mask = input_ids.repeat_interleave(nrs, dim=0), attention_mask.repeat_interleave(nrs, dim=0)
             max_length = input_ids.shape[1] + int(max_new_tokens)
+            if int(top_k) < 0:
+                raise ValueError(f"generate(): top_k = {top_k} (0: no top-k warper, the full softmax)")
             dec = self._model_step(input_ids, attention_mask, encoder_hidden_states, nrs, max_length, use_cache)
+            if int(top_k) == 0:
+                return self._rollout(dec, input_ids, max_length, eos_token_id, pad_token_id, sample_noise, True)[0]
             return self._sample(dec, input_ids, max_length, int(top_k), eos_token_id, pad_token_id, sample_noise)
         dev = input_ids.device
         B, cur = input_ids.shape
@@ -442,6 +495,104 @@ class BertForMaskedLM(nn.Module):
             if not bool(unfinished.any()) or ids.shape[1] >= max_length:
                 break
         return ids
+
+    def _rollout(self, dec, ids, max_length, eos_token_id, pad_token_id, noise, do_sample):
+        """Decode loop on the device over the model step `dec` (of _model_step): per step ONE draw per row from the full softmax
+        (ops.vocab_sample; uniform numbers from `noise` [rows, max_new_tokens] or torch's device generator) or, do_sample=False, the argmax.
+        Rows that have produced eos emit pad from then on; stops when every row has finished or max_length is reached (one flag read per
+        step, as _sample).  Returns (ids [rows, <= max_length], log P(chosen token) per step fp32 [rows, steps], 0 on finished rows)."""
+        dev = ids.device
+        B = ids.shape[0]
+        pad = int(pad_token_id) if pad_token_id is not None else 0
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        step, logps = 0, []
+        while True:
+            logits = dec.next_token_logits(ids).float()
+            if do_sample:
+                u = noise[:, step].to(dev, torch.float32) if noise is not None else torch.rand(B, device=dev)
+                tok, lp = ops.vocab_sample(logits, u, unfinished=unfinished if eos_token_id is not None else None,
+                                              eos_token_id=eos_token_id, pad_token_id=pad)
+            else:
+                tok = logits.argmax(-1)
+                lp = logits.gather(1, tok[:, None])[:, 0] - torch.logsumexp(logits, dim=-1)
+                if eos_token_id is not None:
+                    tok = torch.where(unfinished, tok, torch.full_like(tok, pad))
+                    lp = torch.where(unfinished, lp, torch.zeros_like(lp))
+                    unfinished = unfinished & (tok != eos_token_id)
+            ids = torch.cat([ids, tok.view(-1, 1)], dim=1)
+            logps.append(lp)
+            step += 1
+            if ids.shape[1] >= max_length or not bool(unfinished.any()):
+                break
+        return ids, torch.stack(logps, dim=1)
+
+    @torch.no_grad()
+    def scst_rollout(self, input_ids, attention_mask, encoder_hidden_states, max_new_tokens, eos_token_id, pad_token_id, do_sample=True,
+                     sample_noise=None, num_return_sequences=1, use_cache=True):
+        """The no-grad roll-out of generate_scst: (ids [R n, P + T], the roll-out's own log P(chosen token) fp32 [R n, T]) for R prompt
+        rows, n = num_return_sequences rows per condition set (sample-major, sampling only) and T = max_new_tokens; both are padded
+        (pad_token_id / 0) after a row's eos up to the full width.  The model runs without dropout, whatever self.training says."""
+        nrs = int(num_return_sequences)
+        if nrs < 1 or (nrs != 1 and not do_sample):
+            raise ValueError("scst_rollout(): num_return_sequences > 1 is provided for sampling (do_sample=True) only")
+        T = int(max_new_tokens)
+        if T < 1:
+            raise ValueError(f"scst_rollout(): max_new_tokens = {max_new_tokens}")
+        if sample_noise is not None and (not do_sample or tuple(sample_noise.shape) != (input_ids.shape[0] * nrs, T)):
+            raise ValueError(f"scst_rollout(): sample_noise is [rows, max_new_tokens] = [{input_ids.shape[0] * nrs}, {T}] uniform numbers "
+                             "of a sampled roll-out")
+        if nrs > 1:
+            input_ids, attention_mask = input_ids.repeat_interleave(nrs, dim=0), attention_mask.repeat_interleave(nrs, dim=0)
+        max_length = input_ids.shape[1] + T
+        dec = self._model_step(input_ids, attention_mask, encoder_hidden_states, nrs, max_length, use_cache)
+        ids, lp = self._rollout(dec, input_ids, max_length, eos_token_id, pad_token_id, sample_noise, do_sample)
+        short = max_length - ids.shape[1]
+        if short:      # every row finished early
+            ids = torch.cat([ids, ids.new_full((ids.shape[0], short), int(pad_token_id) if pad_token_id is not None else 0)], dim=1)
+            lp = torch.cat([lp, lp.new_zeros(lp.shape[0], short)], dim=1)
+        return ids, lp
+
+    def sequence_logprobs(self, input_ids, attention_mask, encoder_hidden_states=None, prompt_len=None, eos_token_id=None,
+                          pad_token_id=None):
+        """log P(token) of every generated position of finished sequences, fp32 [R, T], in ONE differentiable pass (two_stream_inputs:
+        about 2 T rows per sequence instead of the reference's T passes over the growing prefix, bert.py:1230-2102).
+        input_ids [R, P + T] with P = prompt_len; attention_mask: the prompt's 3-D mask [R, P, P] (or the grown [R, P + T, P + T]);
+        encoder_hidden_states [R, E, D] or None.  Entry [r, t] = log softmax(logits of step t)[input_ids[r, P + t]]; positions after a
+        row's first eos_token_id are exactly 0, value and gradient (they hold pad_token_id, which is not looked at).  Differentiable with
+        respect to the BERT and LM-head parameters and encoder_hidden_states; BERT's dropout applies when self.training.  Only the T
+        mask-stream rows go through the 768 x 30522 head (functional.LMHeadLogProbFn)."""
+        if prompt_len is None:
+            raise ValueError("sequence_logprobs(): prompt_len is required")
+        P = int(prompt_len)
+        L = input_ids.shape[1]
+        ids2, mask2, pos = two_stream_inputs(input_ids, attention_mask, P, self.tokenizer.mask_token_id)
+        if L > self.config["max_position_embeddings"]:
+            raise ValueError(f"sequence_logprobs(): {L} positions exceed the position table")
+        targets = input_ids[:, P:]
+        targets = torch.where(first_eos_valid(targets, eos_token_id), targets, torch.full_like(targets, -100))
+        seq = self.bert(ids2, mask2, encoder_hidden_states, position_ids=pos).last_hidden_state
+        return Fn.LMHeadLogProbFn.apply(seq[:, L - 1:], targets, *self._head_params())
+
+    def generate_scst(self, input_ids, attention_mask, encoder_hidden_states, max_new_tokens, eos_token_id, pad_token_id, do_sample=True,
+                      sample_noise=None, num_return_sequences=1, use_cache=True, return_rollout_logprobs=False):
+        """Self-critical sequence training's sampler (the reference's sample_scst, bert.py:1230-1502): (ids [R n, P + T], logprobs fp32
+        [R n, T]) - ids from a no-grad roll-out (scst_rollout: one draw per step from the full softmax, or greedy with do_sample=False),
+        logprobs = sequence_logprobs(ids) with a gradient, over condition tokens expanded to one copy per row.
+        Two differences from the reference: the roll-out runs without dropout (with the cache it is the inference decode) while the
+        scoring pass applies BERT's dropout when self.training; positions after a row's eos carry 0 (the reference leaves the log-prob of
+        a token that is not in ids there, bert.py:1454-1461, and every caller masks it).
+        return_rollout_logprobs: also the roll-out's own per-step log-probs [R n, T] (no gradient; tests tie the two paths with it)."""
+        nrs = int(num_return_sequences)
+        ids, step_lp = self.scst_rollout(input_ids, attention_mask, None if encoder_hidden_states is None else encoder_hidden_states.detach(),
+                                         max_new_tokens, eos_token_id, pad_token_id, do_sample=do_sample, sample_noise=sample_noise,
+                                         num_return_sequences=nrs, use_cache=use_cache)
+        cond = encoder_hidden_states
+        if nrs > 1:
+            attention_mask = attention_mask.repeat_interleave(nrs, dim=0)
+            cond = cond.repeat_interleave(nrs, dim=0) if cond is not None else None
+        logprobs = self.sequence_logprobs(ids, attention_mask, cond, prompt_len=input_ids.shape[1], eos_token_id=eos_token_id,
+                                          pad_token_id=pad_token_id)
+        return (ids, logprobs, step_lp) if return_rollout_logprobs else (ids, logprobs)
 
 
 class _RecomputingStep:

@@ -345,4 +345,4 @@ class MiCo(MMGeneralModule):
     # forward(batch, task, compute_loss): task grammar "ret%tv%ta..._cap%tv..." (vast.py:317-348); sub-task letters
     # v = vision (image/video), a = audio, d = depth; fused conditions "va" (contra_head_va) and "vd" (contra_head_id).
     # ------------------------------------------------------------------------------------------------------------------
-    from .mico_forward import forward, forward_qa, encode_batch, _feat_cond, _condition_feats   # noqa: E402,F401
+    from .mico_forward import forward, forward_qa, forward_scst, encode_batch, _feat_cond, _condition_feats   # noqa: E402,F401

@@ -18,6 +18,7 @@ import torch
 from .. import distributed as D
 from .. import functional as Fn, ops
 from .. import runtime
+from .bert import first_eos_valid
 
 COND_MODALITY = {"v": "vision", "a": "audio", "d": "depth"}
 FUSED_HEADS = {"v": "contra_head_v", "a": "contra_head_a", "d": "contra_head_d", "s": "contra_head_s", "va": "contra_head_va",
@@ -321,6 +322,70 @@ def forward_qa(self, batch, task, compute_loss=True):
             continue
         out[f"generated_answers_{st}"] = _generate_text(self, cond, self.max_answer_len, prefix=(q_ids, q_mask), num_beams=self.beam_size,
                                                         length_penalty=1.0, rows_per_condition=rows)
+    return out
+
+
+def forward_scst(self, batch, task, reward_fn, num_samples=1, sample_noise=None):
+    """Self-critical sequence training of the captioner (the reference's --scst_finetuning; model/bert.py:1230-2102), task strings "cap%tv",
+    "cap%tva%tv", ...  Per sub-task and sample: one greedy caption (the baseline) and num_samples sampled ones from the full softmax
+    (BertForMaskedLM.scst_rollout: max_caption_len new tokens from the prompt [CLS], eos [SEP]; config decode_use_cache picks the cached
+    decode), decoded to strings, then
+        reward_fn(captions: list[str], sample_index: list[int], batch) -> one float per caption
+    is called once for the greedy captions (sample_index = 0 .. b - 1) and once for the sampled ones (row b * num_samples + i belongs to sample
+    b: sample_index = [0] * num_samples + [1] * num_samples + ...).  The project ships no reward (no CIDEr): reward_fn is the caller's, it sees
+    the batch for its references (e.g. batch["raw_captions"]), and only reward differences matter.  With the advantage
+    a[row] = r_sample[row] - r_greedy[sample of row] and logprobs = sequence_logprobs(sampled ids) (one differentiable two-stream pass over the
+    SAMPLED rows only, its own cross-attention K/V projected from the expanded condition tokens),
+        loss_scst = - sum_rows,t a[row] * logprobs[row, t] / #(sampled tokens up to and including each row's eos),
+    averaged over sub-tasks; gradients reach BERT, the LM head and, through the condition tokens, the towers, as for loss_cap.
+    sample_noise: fp32 [b * num_samples, max_caption_len] uniform numbers in [0, 1) for the draws (or {sub-task: such a tensor}); None: torch's
+    generator.  Returns {"loss_scst", "reward_sample", "reward_greedy" (means, fp32 scalars), "sampled_captions_<st>", "greedy_captions_<st>"}.
+    No staged (backward_scale) form."""
+    kind, *subtasks = str(task).split("%")
+    if kind != "cap" or not subtasks or "_" in str(task):
+        raise ValueError(f"forward_scst: task {task!r} is not of the form cap%<sub-task>%...")
+    for st in subtasks:
+        if st not in SUBTASKS:
+            raise ValueError(f"forward_scst: unknown sub-task {st!r} in {task!r}")
+    if not callable(reward_fn):
+        raise TypeError("forward_scst: reward_fn(captions, sample_index, batch) -> sequence of float is required (the project ships no reward)")
+    K = int(num_samples)
+    if K < 1:
+        raise ValueError(f"forward_scst: num_samples = {num_samples}")
+    batch = dict(batch) if not isinstance(batch, dict) else batch
+    me = self.multimodal_encoder
+    tk = me.tokenizer
+    T = int(self.max_caption_len)
+    use_cache = bool(self.config.get("decode_use_cache", False))
+    # (the towers and the condition packing only: the caption text is the reward's business, no text pass is needed here)
+    enc = encode_batch(self, {k: v for k, v in batch.items() if k not in ("raw_captions", "input_ids", "attention_mask", "caption_tokens")})
+    out, losses, r_s_all, r_g_all = {}, [], [], []
+    for st in subtasks:
+        cond = _condition_feats(self, enc, st[1:])
+        b, dev = cond.shape[0], cond.device
+        noise = sample_noise.get(st) if isinstance(sample_noise, dict) else sample_noise
+        prompt = torch.full((b, 1), tk.bos_token_id, dtype=torch.long, device=dev)
+        mask = prompt.new_ones(b, 1, 1)
+        roll = dict(max_new_tokens=T, eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=use_cache)
+        g_ids, _ = me.scst_rollout(prompt, mask, cond.detach(), do_sample=False, **roll)
+        s_ids, _ = me.scst_rollout(prompt, mask, cond.detach(), do_sample=True, sample_noise=noise, num_return_sequences=K, **roll)
+        logp = me.sequence_logprobs(s_ids, mask.repeat_interleave(K, dim=0), cond.repeat_interleave(K, dim=0), prompt_len=1,
+                                    eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id)
+        caps_g = tk.batch_decode(g_ids[:, 1:], skip_special_tokens=True)
+        caps_s = tk.batch_decode(s_ids[:, 1:], skip_special_tokens=True)
+        owner = [i // K for i in range(b * K)]
+        r_g = torch.as_tensor(list(reward_fn(caps_g, list(range(b)), batch)), dtype=torch.float32, device=logp.device)
+        r_s = torch.as_tensor(list(reward_fn(caps_s, owner, batch)), dtype=torch.float32, device=logp.device)
+        if r_g.shape != (b,) or r_s.shape != (b * K,):
+            raise ValueError(f"forward_scst: reward_fn returned {r_g.numel()} / {r_s.numel()} rewards for {b} / {b * K} captions")
+        adv = r_s - r_g.repeat_interleave(K)
+        n_valid = first_eos_valid(s_ids[:, 1:], tk.sep_token_id).sum().clamp_min(1).to(torch.float32)
+        losses.append(-(adv[:, None] * logp).sum() / n_valid.to(logp.device))
+        r_s_all.append(r_s.mean())
+        r_g_all.append(r_g.mean())
+        out[f"sampled_captions_{st}"], out[f"greedy_captions_{st}"] = caps_s, caps_g
+    out["loss_scst"] = sum(losses) / len(losses)
+    out["reward_sample"], out["reward_greedy"] = sum(r_s_all) / len(r_s_all), sum(r_g_all) / len(r_g_all)
     return out
 
 

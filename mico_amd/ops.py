@@ -599,6 +599,43 @@ def ce_fwd_bwd(logits, target, *, cols=None, ignore_index=-100, label_smoothing=
           "mico_ce_fwd_bwd")
 
 
+def logprob_fwd_bwd(logits, target, *, cols=None, ignore_index=-100, row_logp=None, dlogits=None, row_gscale=None, gscale=1.0):
+    """Per-row log P(target) and / or its gradient with one upstream gradient per row; see mico_logprob_fwd_bwd."""
+    rows = logits.shape[0]
+    cols = cols if cols is not None else logits.shape[1]
+    if dlogits is not None and (dlogits.dtype != logits.dtype or row_gscale is None or row_gscale.dtype != torch.float32
+                                or row_gscale.numel() != rows or not row_gscale.is_contiguous()):
+        raise MicoHipError("logprob_fwd_bwd: dlogits has the logits' dtype and needs row_gscale, contiguous fp32 [rows]")
+    check(_lib.lib().mico_logprob_fwd_bwd(_p(logits), dt_code(logits.dtype), logits.stride(0), rows, cols, _p(target), ignore_index,
+                                          _p(row_logp), _p(dlogits), dlogits.stride(0) if dlogits is not None else 0, _p(row_gscale),
+                                          float(gscale), _st()), "mico_logprob_fwd_bwd")
+
+
+def vocab_sample(logits, u, *, cols=None, unfinished=None, eos_token_id=None, pad_token_id=0):
+    """(token int64 [rows], logp fp32 [rows]): one inverse-CDF draw per row of the fp32 logits [rows, >= cols] (any row stride) from
+    softmax(logits[:, :cols]) with the uniform numbers u fp32 [rows]; see mico_vocab_sample.  unfinished: bool / uint8 [rows], updated in
+    place - finished rows emit pad_token_id with logp 0, a row that draws eos_token_id becomes finished."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise MicoHipError(f"vocab_sample takes a 2-D fp32 matrix with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    rows = logits.shape[0]
+    cols = int(cols) if cols is not None else logits.shape[1]
+    if not 0 < cols <= logits.shape[1]:
+        raise MicoHipError(f"vocab_sample: cols = {cols} of a row of {logits.shape[1]}")
+    if u.dtype != torch.float32 or u.numel() != rows:
+        raise MicoHipError("vocab_sample: u is fp32 [rows]")
+    if unfinished is not None and (unfinished.dtype not in (torch.bool, torch.uint8) or unfinished.numel() != rows
+                                   or not unfinished.is_contiguous()):
+        raise MicoHipError("vocab_sample: unfinished is a contiguous bool / uint8 [rows] tensor")
+    token = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if rows == 0:
+        return token, logp
+    check(_lib.lib().mico_vocab_sample(_p(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), cols), rows, cols,
+                                       _p(u.contiguous()), _p(unfinished), -1 if eos_token_id is None else int(eos_token_id),
+                                       int(pad_token_id or 0), _p(token), _p(logp), _st()), "mico_vocab_sample")
+    return token, logp
+
+
 def token_mask(tokens, mask_prob, u_mask, u_kind, u_tok, mask_token, range_start, range_end):
     """(masked token ids, labels) of the caption loss's TokenMasker on the device; see mico_token_mask.  u_mask [rounds, rows, S]."""
     rows, S = tokens.shape

@@ -564,6 +564,27 @@ int mico_adamw_step(const mico_adamw_tensor* tensors, int n_tensors, const int* 
  * .g / .numel of each entry are read) is inf or NaN; *flag is left untouched otherwise (the caller zeroes it). */
 int mico_grads_finite(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
                       int nchunks, int chunk_elems, float* flag, void* stream);
+/* Global-norm gradient clipping (ABI 120; torch.nn.utils.clip_grad_norm_ with norm_type 2, the commented-out call of
+ * data/utils/pipeline.py:102-103 and --grad_norm of data/utils/args.py:230) without a pass of its own over the gradients and without a host read:
+ *   mico_grad_sumsq:     chunk_sumsq[c] = sum over chunk c of (g * grad_mult)^2 (the multiply first: a loss-scaled gradient need not be squarable),
+ *                        one workgroup and one plain store per chunk, fixed summation order (the same bits on every run; at most 31 fp32
+ *                        roundings on any element's path with chunk_elems = 65536).  In the same read: *flag = 1.0f if any gradient is inf / NaN,
+ *                        left untouched otherwise - mico_grads_finite's rule, so this launch REPLACES that one (flag may be NULL).  Only .g /
+ *                        .numel of each entry are read.
+ *   mico_grad_clip_coef: *total_norm = sqrt(sum_c chunk_sumsq[c]) (summed in fp64, fixed order), *coef = min(1, max_norm / (*total_norm + 1e-6));
+ *                        both fp32 device scalars.  max_norm > 0.  A non-finite norm is not special-cased (inf -> coef 0, NaN -> NaN, as torch).
+ *   mico_adamw_step_dev: mico_adamw_step with every gradient multiplied by grad_mult * *mult_dev (the product formed once; mult_dev = NULL
+ *                        means 1: the same kernel, the same launch).  With *mult_dev == 1.0f the step is bit-identical to mico_adamw_step's.
+ *   mico_grads_scale:    g *= *mult_dev in place over .g / .numel of each entry (the gradients are written although the descriptor declares them
+ *                        const); nothing is written when *mult_dev == 1.0f. */
+int mico_grad_sumsq(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                    int nchunks, int chunk_elems, float grad_mult, float* chunk_sumsq, float* flag, void* stream);
+int mico_grad_clip_coef(const float* chunk_sumsq, int nchunks, float max_norm, float* total_norm, float* coef, void* stream);
+int mico_adamw_step_dev(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                        int nchunks, int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
+                        float step_size, float grad_mult, const float* mult_dev, void* stream);
+int mico_grads_scale(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                     int nchunks, int chunk_elems, const float* mult_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Swin tower pieces (model/swin.py).  Everything else of the tower runs on the entry points above (patch

@@ -131,6 +131,10 @@ PROTOTYPES = {
     "mico_fbank_windows": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_f, c_f, c_vp, c_vp],
     "mico_adamw_step": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp],
     "mico_grads_finite": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp],
+    "mico_grad_sumsq": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp, c_vp],
+    "mico_grad_clip_coef": [c_vp, c_int, c_f, c_vp, c_vp, c_vp],
+    "mico_adamw_step_dev": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp],
+    "mico_grads_scale": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp],
     "mico_comm_unique_id": [c_vp],
     "mico_comm_init": [C.POINTER(c_vp), c_int, c_int, c_vp],
     "mico_comm_destroy": [c_vp],
@@ -149,7 +153,7 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 119   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 120   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):

@@ -120,13 +120,17 @@ __global__ void fbank_windows_kernel(const float* __restrict__ fbank, int T, int
 // ---- multi-tensor AdamW (data/utils/build_optimizer.py:105-197) ---------------------------------------------------------
 __global__ __launch_bounds__(256) void adamw_kernel(const mico_adamw_tensor* __restrict__ tensors, const int* __restrict__ chunk_tensor,
                                                     const int64_t* __restrict__ chunk_start, int chunk_elems, float lr, float beta1,
-                                                    float beta2, float eps, float wd, float step_size, float grad_mult) {
+                                                    float beta2, float eps, float wd, float step_size, float grad_mult,
+                                                    const float* __restrict__ mult_dev) {
     const mico_adamw_tensor t = tensors[chunk_tensor[blockIdx.x]];
     const int64_t s0 = chunk_start[blockIdx.x];
     const int64_t s1 = min(t.numel, s0 + (int64_t)chunk_elems);
     const float ob1 = 1.f - beta1, ob2 = 1.f - beta2;
+    // mult_dev (NULL: 1): the clip coefficient of mico_grad_clip_coef, read from device memory so no host sync sits between the norm and the
+    // update.  The product is formed ONCE, so a coefficient of exactly 1.0f leaves the step bit-identical to the one without it.
+    const float gm = mult_dev ? grad_mult * *mult_dev : grad_mult;
     auto upd = [&](float p, float g, float& m, float& v) {
-        g *= grad_mult;     // 1 / loss scale (GradScaler.unscale_ folded into the update: no pass of its own over the gradients)
+        g *= gm;            // 1 / loss scale (GradScaler.unscale_ folded into the update: no pass of its own over the gradients)
         m = m * beta1 + ob1 * g;
         v = v * beta2 + ob2 * g * g;
         p = p - step_size * (m / (sqrtf(v) + eps));
@@ -534,15 +538,183 @@ extern "C" int mico_grads_finite(const mico_adamw_tensor* tensors, int n_tensors
     return MICO_OK;
 }
 
+// the one launch path of the AdamW kernel: mico_adamw_step (mult_dev = NULL) and mico_adamw_step_dev
+static int adamw_launch(const char* who, const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                        int nchunks, int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay, float step_size,
+                        float grad_mult, const float* mult_dev, void* stream) {
+    MICO_CHECK(tensors && chunk_tensor && chunk_start && n_tensors > 0, "%s: null table", who);
+    MICO_CHECK(chunk_elems > 0 && chunk_elems % 4 == 0, "%s: chunk_elems must be a positive multiple of 4", who);
+    MICO_CHECK(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "%s: bad hyper-parameters", who);
+    if (nchunks <= 0) return MICO_OK;
+    MICO_LAUNCH(adamw_kernel, dim3(nchunks), dim3(256), 0, ST, tensors, chunk_tensor, chunk_start, chunk_elems, lr, beta1, beta2, eps,
+                weight_decay, step_size, grad_mult, mult_dev);
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
 extern "C" int mico_adamw_step(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
                                int nchunks, int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
                                float step_size, float grad_mult, void* stream) {
-    MICO_CHECK(tensors && chunk_tensor && chunk_start && n_tensors > 0, "mico_adamw_step: null table");
-    MICO_CHECK(chunk_elems > 0 && chunk_elems % 4 == 0, "mico_adamw_step: chunk_elems must be a positive multiple of 4");
-    MICO_CHECK(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "mico_adamw_step: bad hyper-parameters");
+    return adamw_launch("mico_adamw_step", tensors, n_tensors, chunk_tensor, chunk_start, nchunks, chunk_elems, lr, beta1, beta2, eps,
+                        weight_decay, step_size, grad_mult, nullptr, stream);
+}
+
+extern "C" int mico_adamw_step_dev(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                                   int nchunks, int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                   float step_size, float grad_mult, const float* mult_dev, void* stream) {
+    return adamw_launch("mico_adamw_step_dev", tensors, n_tensors, chunk_tensor, chunk_start, nchunks, chunk_elems, lr, beta1, beta2, eps,
+                        weight_decay, step_size, grad_mult, mult_dev, stream);
+}
+
+// ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) ----------------------------------------------------
+// Sum of squares of one chunk of (g * grad_mult), and the inf / NaN flag of grads_finite_kernel in the same read of the gradients.
+// One plain store per workgroup and a fixed summation tree: the same bits on every run.
+// Longest summation chain of one element's term (all terms >= 0, so the relative error of the sum is <= chain * 2^-24):
+//   1 multiply + 1 square + at most 17 sequential adds into one of a lane's 16 accumulators (aligned path: a full chunk is 64 f32x4 reads
+//   per lane, 4 per trip, and a ragged end adds one more; misaligned path: 256 scalar reads per lane, 16 per trip, the rest one accumulator
+//   each) + 4 levels joining the 16 accumulators + 6 shuffle levels across the wave + 2 levels across the 4 waves = 31 roundings with
+//   chunk_elems = 65536 (the chain grows by one per 4096 elements of a chunk); mico_grad_clip_coef then adds the chunk sums in fp64.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const mico_adamw_tensor* __restrict__ tensors, const int* __restrict__ chunk_tensor,
+                                                         const int64_t* __restrict__ chunk_start, int chunk_elems, float grad_mult,
+                                                         float* __restrict__ chunk_sumsq, float* __restrict__ flag) {
+    __shared__ float wave_part[4];
+    const mico_adamw_tensor t = tensors[chunk_tensor[blockIdx.x]];
+    const int64_t s0 = chunk_start[blockIdx.x], s1 = min(t.numel, s0 + (int64_t)chunk_elems);
+    f32x4 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bool bad = false;
+    auto nonfinite = [](float g) { return !(fabsf(g) <= 3.4e38f); };
+    const bool vec = (((uintptr_t)t.g) & 15) == 0 && (s0 & 3) == 0;
+    if (vec) {
+        int64_t i = s0 + threadIdx.x * 4;
+        for (; i + 3 * 1024 + 3 < s1; i += 4 * 1024) {     // 4 independent 16-byte reads in flight per lane
+            f32x4 g[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) g[u] = *(const f32x4*)(t.g + i + u * 1024);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                bad |= nonfinite(g[u][0]) | nonfinite(g[u][1]) | nonfinite(g[u][2]) | nonfinite(g[u][3]);
+                const f32x4 x = g[u] * grad_mult;          // the multiply comes BEFORE the square: a scaled gradient may not be squarable
+                acc[u] += x * x;
+            }
+        }
+        for (int u = 0; i + 3 < s1; i += 1024, ++u) {      // at most 3 more reads per lane
+            const f32x4 g = *(const f32x4*)(t.g + i);
+            bad |= nonfinite(g[0]) | nonfinite(g[1]) | nonfinite(g[2]) | nonfinite(g[3]);
+            const f32x4 x = g * grad_mult;
+            acc[u & 3] += x * x;
+        }
+        // ragged tail of the tensor (numel % 4): the first threads, one element each
+        const int64_t tail0 = s1 - ((s1 - s0) & 3);
+        i = tail0 + threadIdx.x;
+        if (i < s1) {
+            const float g = t.g[i];
+            bad |= nonfinite(g);
+            const float x = g * grad_mult;
+            acc[3][3] += x * x;
+        }
+    } else {
+        int64_t i = s0 + threadIdx.x;
+        for (; i + 15 * 256 < s1; i += 16 * 256) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float g = t.g[i + (u * 4 + k) * 256];
+                    bad |= nonfinite(g);
+                    const float x = g * grad_mult;
+                    acc[u][k] += x * x;
+                }
+            }
+        }
+        for (int u = 0; i < s1; i += 256, ++u) {           // at most 15 more reads per lane, one accumulator each
+            const float g = t.g[i];
+            bad |= nonfinite(g);
+            const float x = g * grad_mult;
+            acc[(u >> 2) & 3][u & 3] += x * x;
+        }
+    }
+    const f32x4 a = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    float s = (a[0] + a[1]) + (a[2] + a[3]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const bool wave_bad = __any(bad);
+    if ((threadIdx.x & 63) == 0) {
+        wave_part[threadIdx.x >> 6] = s;
+        if (flag && wave_bad) *flag = 1.f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_sumsq[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+
+// total_norm = sqrt(sum of the chunk sums), coef = min(1, max_norm / (total_norm + 1e-6)): one workgroup, fp64, fixed order (lane l adds
+// chunks l, l + 256, ... in sequence, then a tree over the 256 lanes).  A non-finite norm is not special-cased (torch: inf -> coef 0, NaN -> NaN).
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ chunk_sumsq, int nchunks, float max_norm,
+                                                             float* __restrict__ total_norm, float* __restrict__ coef) {
+    __shared__ double part[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nchunks; i += 256) s += (double)chunk_sumsq[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float tn = (float)sqrt(part[0]);
+        const float c = max_norm / (tn + 1e-6f);
+        *total_norm = tn;
+        *coef = c > 1.f ? 1.f : c;      // (not fminf: a NaN norm gives a NaN coefficient, as torch's clamp does)
+    }
+}
+
+// g *= *mult_dev in place (mico_amd.optim.clip_grad_norm_: the drop-in for callers that do not step through mico_adamw_step_dev)
+__global__ __launch_bounds__(256) void grads_scale_kernel(const mico_adamw_tensor* __restrict__ tensors, const int* __restrict__ chunk_tensor,
+                                                          const int64_t* __restrict__ chunk_start, int chunk_elems,
+                                                          const float* __restrict__ mult_dev) {
+    const float mult = *mult_dev;
+    if (mult == 1.f) return;            // nothing to clip: the gradients keep their bits and the pass costs no traffic
+    const mico_adamw_tensor t = tensors[chunk_tensor[blockIdx.x]];
+    const int64_t s0 = chunk_start[blockIdx.x], s1 = min(t.numel, s0 + (int64_t)chunk_elems);
+    float* g = const_cast<float*>(t.g);
+    const bool vec = (((uintptr_t)g) & 15) == 0 && (s0 & 3) == 0;
+    if (vec) {
+        int64_t i = s0 + threadIdx.x * 4;
+        for (; i + 3 < s1; i += 256 * 4) *(f32x4*)(g + i) = *(const f32x4*)(g + i) * mult;
+        const int64_t tail0 = s1 - ((s1 - s0) & 3);
+        i = tail0 + threadIdx.x;
+        if (i < s1) g[i] *= mult;
+    } else {
+        for (int64_t i = s0 + threadIdx.x; i < s1; i += 256) g[i] *= mult;
+    }
+}
+
+extern "C" int mico_grad_sumsq(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                               int nchunks, int chunk_elems, float grad_mult, float* chunk_sumsq, float* flag, void* stream) {
+    MICO_CHECK(tensors && chunk_tensor && chunk_start && chunk_sumsq && n_tensors > 0, "mico_grad_sumsq: null table");
+    MICO_CHECK(chunk_elems > 0 && chunk_elems % 4 == 0, "mico_grad_sumsq: chunk_elems must be a positive multiple of 4");
     if (nchunks <= 0) return MICO_OK;
-    MICO_LAUNCH(adamw_kernel, dim3(nchunks), dim3(256), 0, ST, tensors, chunk_tensor, chunk_start, chunk_elems, lr, beta1, beta2, eps,
-                weight_decay, step_size, grad_mult);
+    MICO_LAUNCH(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, ST, tensors, chunk_tensor, chunk_start, chunk_elems, grad_mult, chunk_sumsq,
+                flag);
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_grad_clip_coef(const float* chunk_sumsq, int nchunks, float max_norm, float* total_norm, float* coef, void* stream) {
+    MICO_CHECK(total_norm && coef && nchunks >= 0 && (chunk_sumsq || nchunks == 0), "mico_grad_clip_coef: bad args");
+    MICO_CHECK(max_norm > 0.f, "mico_grad_clip_coef: max_norm must be positive");
+    MICO_LAUNCH(grad_clip_coef_kernel, dim3(1), dim3(256), 0, ST, chunk_sumsq, nchunks, max_norm, total_norm, coef);
+    MICO_LAUNCH_CHECK();
+    return MICO_OK;
+}
+
+extern "C" int mico_grads_scale(const mico_adamw_tensor* tensors, int n_tensors, const int* chunk_tensor, const int64_t* chunk_start,
+                                int nchunks, int chunk_elems, const float* mult_dev, void* stream) {
+    MICO_CHECK(tensors && chunk_tensor && chunk_start && mult_dev && n_tensors > 0, "mico_grads_scale: null table");
+    MICO_CHECK(chunk_elems > 0 && chunk_elems % 4 == 0, "mico_grads_scale: chunk_elems must be a positive multiple of 4");
+    if (nchunks <= 0) return MICO_OK;
+    MICO_LAUNCH(grads_scale_kernel, dim3(nchunks), dim3(256), 0, ST, tensors, chunk_tensor, chunk_start, chunk_elems, mult_dev);
     MICO_LAUNCH_CHECK();
     return MICO_OK;
 }

@@ -3,7 +3,10 @@
 Specification: the VAST sibling's trainer-facing forward (data/model/vast.py:317-348), forward_ret (:383-464: ITC with
 label smoothing 0.1 against the all-gathered global batch, ITM with in-batch hard negatives) and forward_cap (:485-512:
 causal masked-caption LM), generalised with MiCo's depth heads (model/mico.py:390,392,402,406).  These functions become
-methods of mico_amd.model.mico.MiCo.  The question-answering family ("qa%...", vast.py:557-650) has an entry of its own: forward_qa below.
+methods of mico_amd.model.mico.MiCo.
+
+Entry points: forward (direct, or _forward_staged; evaluation: _eval_ret / _eval_cap), forward_qa ("qa%...", vast.py:557-650), forward_scst,
+encode_batch; task strings go through _parse_task, text through _tokenize.  One definition each: _itm_draw, _itm_loss, _cap_loss, _cls_prompt.
 
 batch keys: vision_pixels [b,n,3,h,w] | audio_spectrograms [b,n,h,w] | depth_pixels [b,n,3,h,w] (any subset);
             raw_captions (list[str]) or input_ids/attention_mask [b,S].
@@ -13,6 +16,8 @@ batch keys: vision_pixels [b,n,3,h,w] | audio_spectrograms [b,n,h,w] | depth_pix
             (torch.multinomial / TokenMasker) for parity tests, "drop_path_scale" / "patch_keep" ({modality: [depth, 2, b*n] /
             int [b*n, keep]}) the tower's stochastic-depth and patch-dropout draws; optional `_world`: simulated gathered tensors.
 """
+import collections
+
 import torch
 
 from .. import distributed as D
@@ -25,6 +30,33 @@ FUSED_HEADS = {"v": "contra_head_v", "a": "contra_head_a", "d": "contra_head_d",
                "vd": "contra_head_id", "vs": "contra_head_vs", "vas": "contra_head_vas"}
 _UNKNOWN_FAMILY = "{}: MiCo.forward runs the ret% / itc% / cap% families; question answering (qa%...) is MiCo.forward_qa"
 SUBTASKS = ("tv", "ta", "td", "ts", "tva", "tvd", "tvs", "tvas")    # vast.py's tv / ta / tva / tvs / tvas + MiCo's depth heads
+_FAMILIES = {"forward": ("ret", "itc", "cap"), "forward_qa": ("qa",), "forward_scst": ("cap",)}
+
+
+def _parse_task(task, entry):
+    """[(family, [sub-task, ...]), ...] of a task string like "ret%tva%tv_cap%tva" for the entry point `entry` (a key of _FAMILIES).  forward
+    takes any number of its families and raises NotImplementedError for another one; forward_qa and forward_scst take exactly one family with
+    at least one sub-task and raise ValueError otherwise.  A sub-task outside SUBTASKS is a ValueError for all of them."""
+    parts, parsed = str(task).split("_"), []
+    for t in parts:
+        kind, *subtasks = t.split("%")
+        if entry == "forward":
+            if kind not in _FAMILIES[entry]:
+                raise NotImplementedError(_UNKNOWN_FAMILY.format(t))
+        elif kind not in _FAMILIES[entry] or not subtasks or len(parts) > 1:
+            raise ValueError(f"{entry}: task {task!r} is not of the form {_FAMILIES[entry][0]}%<sub-task>%...")
+        for st in subtasks:
+            if st not in SUBTASKS:
+                raise ValueError(f"{entry}: unknown sub-task {st!r} in {task!r}")
+        parsed.append((kind, subtasks))
+    return parsed
+
+
+def _tokenize(self, texts, max_length):
+    """token ids and key-padding mask [len(texts), max_length] from the BERT tokenizer, on the model's device"""
+    dev = self.contra_temp.device
+    tok = self.multimodal_encoder.tokenizer(texts, padding="max_length", truncation=True, max_length=max_length, return_tensors="pt")
+    return tok.input_ids.to(dev), tok.attention_mask.to(dev)
 
 
 def _tokens(self, batch):
@@ -33,10 +65,7 @@ def _tokens(self, batch):
     if "caption_tokens" in batch:
         ct = batch["caption_tokens"]
         return ct.input_ids, ct.attention_mask
-    dev = self.contra_temp.device
-    tok = self.multimodal_encoder.tokenizer(batch["raw_captions"], padding="max_length", truncation=True,
-                                            max_length=self.max_caption_len, return_tensors="pt")
-    batch["input_ids"], batch["attention_mask"] = tok.input_ids.to(dev), tok.attention_mask.to(dev)
+    batch["input_ids"], batch["attention_mask"] = _tokenize(self, batch["raw_captions"], self.max_caption_len)
     return batch["input_ids"], batch["attention_mask"]
 
 
@@ -80,10 +109,7 @@ def encode_batch(self, batch):
             enc["condition_feats_" + m] = self._pack(COND_MODALITY[m], o)
     if "subtitle_ids" in batch or "raw_subtitles" in batch:   # vast.py:96-104,168-174: subtitles through the text BERT
         if "subtitle_ids" not in batch:
-            dev = self.contra_temp.device
-            tok = self.multimodal_encoder.tokenizer(batch["raw_subtitles"], padding="max_length", truncation=True,
-                                                    max_length=self.max_subtitle_len, return_tensors="pt")
-            batch["subtitle_ids"], batch["subtitle_mask"] = tok.input_ids.to(dev), tok.attention_mask.to(dev)
+            batch["subtitle_ids"], batch["subtitle_mask"] = _tokenize(self, batch["raw_subtitles"], self.max_subtitle_len)
         sub = self.multimodal_encoder.bert(input_ids=batch["subtitle_ids"], attention_mask=batch["subtitle_mask"]).last_hidden_state
         enc["output_s"] = sub
         enc["pooled_s"] = self.pool_text_for_contra(sub)
@@ -107,13 +133,64 @@ def _condition_feats(self, enc, cond):
     return torch.cat([enc["condition_feats_" + m] for m in cond], dim=1)
 
 
+def _share_cross_kv(self):
+    """Share the cross-attention K/V projections between the passes of a training step (runtime.CFG.share_cross_kv)."""
+    return runtime.CFG.share_cross_kv and torch.is_grad_enabled()
+
+
+# What the ITM hard-negative draw of one sub-task leaves for its triplet pass: neg_c [b], the drawn condition rows (indices into the gathered
+# batch); ids1 / am1 [3 b, S], the triplet's token ids and masks [own | own | hard-negative text]; fetch(cond, neg_c) -> the drawn rows'
+# condition tokens.
+_ItmDraw = collections.namedtuple("_ItmDraw", "neg_c ids1 am1 fetch")
+
+
+def _itm_draw(batch, st, sim_c2t, sim_t2c, row0, text, text_all):
+    """The ITM hard negatives of sub-task `st` (vast.py:421-437): injected, or drawn per row and direction from the softmax of the similarities.
+    row0: this rank's first row in the gathered batch; text / text_all: (ids, mask) of this rank / gathered."""
+    inj, world = batch.get("_injected", {}), batch.get("_world")
+    (ids, am), (ids_all, mask_all) = text, text_all
+    bs, dev = ids.shape[0], ids.device
+    if st in inj:
+        neg_c, neg_t = inj[st]["neg_cond_idx"].to(dev), inj[st]["neg_text_idx"].to(dev)
+    else:
+        # one kernel per direction: softmax + 1e-4, own-rank diagonal zeroed, inverse-CDF draw per row (mico_itm_sample) - the
+        # reference loops over rows with a .item() host sync each (vast.py:428-440); `_itm_uniform` injects the random numbers
+        un = inj.get("_itm_uniform", {}).get(st)
+        u_c, u_t = (un[0].to(dev), un[1].to(dev)) if un is not None else (torch.rand(bs, device=dev), torch.rand(bs, device=dev))
+        neg_c = ops.itm_sample(sim_t2c.detach(), row0, u_c.float())
+        neg_t = ops.itm_sample(sim_c2t.detach(), row0, u_t.float())
+    return _ItmDraw(neg_c, torch.cat((ids, ids, ids_all[neg_t]), dim=0), torch.cat((am, am, mask_all[neg_t]), dim=0),
+                    world[f"cond_{st[1:]}_fetch"] if world else D.fetch_rows)
+
+
+def _itm_loss(self, ids1, am1, *, kv=None, cond3=None):
+    """The ITM pass over the triplet [own | hard negative | own] and its loss (vast.py:438-457), against the shared K/V memory kv = (kv_own,
+    kv_neg) of BertModel.project_cross_kv or the triplet's condition tokens cond3 [3 b, E, D]."""
+    bs = ids1.shape[0] // 3
+    out = self.multimodal_encoder.bert(input_ids=ids1, attention_mask=am1, encoder_hidden_states=cond3, cross_kv=kv).last_hidden_state
+    logits = self.itm_head(out[:, 0])
+    gt = torch.zeros(bs * 3, dtype=torch.long, device=ids1.device)
+    gt[:bs] = 1
+    return self.itm_ratio * Fn.cross_entropy(logits, gt)
+
+
+def _itm_direct(self, enc, key, cond, draw):
+    """The direct step's use of a draw, at once: the ITM loss of condition set `key` with the condition tokens `cond`."""
+    cond_neg = draw.fetch(cond, draw.neg_c)
+    if not _share_cross_kv(self):
+        return _itm_loss(self, draw.ids1, draw.am1, cond3=torch.cat((cond, cond_neg, cond), dim=0))
+    # the triplet [own | hard negative | own] holds the batch's own condition tokens twice and the captioning pass reads
+    # them again: their K/V projections are computed once per step (functional.CrossKVFn) and kept for _forward_cap
+    kv = enc.setdefault("_cross_kv", {})[key] = self.multimodal_encoder.bert.project_cross_kv(cond, cond_neg)
+    return _itm_loss(self, draw.ids1, draw.am1, kv=kv)
+
+
 def _forward_ret(self, batch, enc, subtasks, itm=True, deferred=None):
-    """ITC + ITM of vast.py:395-457.  itm=False: the contrastive objective alone (step-A of SURVEY.md section 8d, BASELINE configs[1]) - the
-    ITM hard-negative passes are not run and no "loss_itm" is returned (task prefix "itc%...", an addition of this repo).
-    deferred (dict, staged differentiation - forward(backward_scale=...)): the ITM passes are not run here either; their inputs - the hard-negative
-    draws (same random numbers in the same order as the direct form), the triplet's token ids and masks - are left in deferred[subtask] for
-    _staged_groups, and only "loss_itc" is returned."""
-    inj = batch.get("_injected", {})
+    """ITC + ITM of vast.py:395-457: per sub-task the contrastive loss, the hard-negative draw and the triplet pass, in this order.
+    itm=False: the contrastive objective alone (step-A of SURVEY.md section 8d, BASELINE configs[1]) - nothing is drawn, no ITM pass is run
+    and no "loss_itm" is returned (task prefix "itc%...", an addition of this repo).
+    deferred (dict, the staged step): the draws are made, in the same order, and left in deferred[subtask] for _forward_staged, which runs
+    the passes; only "loss_itc" is returned."""
     world = batch.get("_world")
     ids, am = _tokens(self, batch)
     rank = world["rank"] if world else D.rank()
@@ -134,60 +211,17 @@ def _forward_ret(self, batch, enc, subtasks, itm=True, deferred=None):
         sim_c2t = Fn.matmul_nt(fc, feat_t_all) / self.contra_temp                       # vast.py:405-408
         sim_t2c = Fn.matmul_nt(feat_t, fc_all) / self.contra_temp
         loss_itc.append((Fn.cross_entropy(sim_c2t, targets, 0.1) + Fn.cross_entropy(sim_t2c, targets, 0.1)) / 2)
-        if not itm:
-            continue
-        # ---- ITM hard negatives (vast.py:421-457) ----
-        cond = _condition_feats(self, enc, st[1:]) if deferred is None else None
-        if st in inj:
-            neg_c, neg_t = inj[st]["neg_cond_idx"].to(ids.device), inj[st]["neg_text_idx"].to(ids.device)
-        else:
-            # one kernel per direction: softmax + 1e-4, own-rank diagonal zeroed, inverse-CDF draw per row (mico_itm_sample) - the
-            # reference loops over rows with a .item() host sync each (vast.py:428-440); `_itm_uniform` injects the random numbers
-            un = inj.get("_itm_uniform", {}).get(st)
-            u_c, u_t = (un[0].to(ids.device), un[1].to(ids.device)) if un is not None else (
-                torch.rand(bs, device=ids.device), torch.rand(bs, device=ids.device))
-            neg_c = ops.itm_sample(sim_t2c.detach(), rank * bs, u_c.float())
-            neg_t = ops.itm_sample(sim_c2t.detach(), rank * bs, u_t.float())
-        ids1 = torch.cat((ids, ids, ids_all[neg_t]), dim=0)
-        am1 = torch.cat((am, am, mask_all[neg_t]), dim=0)
-        if deferred is not None:
-            deferred[st] = dict(neg_c=neg_c, ids1=ids1, am1=am1, fetch=world[f"cond_{st[1:]}_fetch"] if world else D.fetch_rows)
-            continue
-        if world:
-            cond_neg = world[f"cond_{st[1:]}_fetch"](cond, neg_c)
-        else:
-            cond_neg = D.fetch_rows(cond, neg_c)
-        if _share_cross_kv(self):
-            # the triplet [own | hard negative | own] holds the batch's own condition tokens twice and the captioning pass reads
-            # them again: their K/V projections are computed once per step (functional.CrossKVFn) and kept for _forward_cap
-            kv = self.multimodal_encoder.bert.project_cross_kv(cond, cond_neg)
-            enc.setdefault("_cross_kv", {})[st[1:]] = kv
-            out = self.multimodal_encoder.bert(input_ids=ids1, attention_mask=am1, cross_kv=kv).last_hidden_state
-        else:
-            cond3 = torch.cat((cond, cond_neg, cond), dim=0)
-            out = self.multimodal_encoder.bert(input_ids=ids1, attention_mask=am1, encoder_hidden_states=cond3).last_hidden_state
-        logits = self.itm_head(out[:, 0])
-        gt = torch.zeros(bs * 3, dtype=torch.long, device=ids.device)
-        gt[:bs] = 1
-        loss_itm.append(self.itm_ratio * Fn.cross_entropy(logits, gt))
-    if not itm or deferred is not None:
-        return {"loss_itc": sum(loss_itc) / len(loss_itc)}
-    return {"loss_itc": sum(loss_itc) / len(loss_itc), "loss_itm": sum(loss_itm) / len(loss_itm)}
-
-
-def _itm_loss(self, kv, ids1, am1):
-    """The ITM pass over the triplet [own | hard negative | own] against a shared K/V memory, and its loss (vast.py:438-457)."""
-    bs = ids1.shape[0] // 3
-    out = self.multimodal_encoder.bert(input_ids=ids1, attention_mask=am1, cross_kv=kv).last_hidden_state
-    logits = self.itm_head(out[:, 0])
-    gt = torch.zeros(bs * 3, dtype=torch.long, device=ids1.device)
-    gt[:bs] = 1
-    return self.itm_ratio * Fn.cross_entropy(logits, gt)
-
-
-def _share_cross_kv(self):
-    """Share the cross-attention K/V projections between the passes of a training step (runtime.CFG.share_cross_kv)."""
-    return runtime.CFG.share_cross_kv and torch.is_grad_enabled()
+        if itm:
+            cond = _condition_feats(self, enc, st[1:]) if deferred is None else None       # (in front of the draw: the direct step's launch order)
+            draw = _itm_draw(batch, st, sim_c2t, sim_t2c, rank * bs, (ids, am), (ids_all, mask_all))
+            if deferred is None:
+                loss_itm.append(_itm_direct(self, enc, st[1:], cond, draw))
+            else:
+                deferred[st] = draw
+    out = {"loss_itc": sum(loss_itc) / len(loss_itc)}
+    if loss_itm:
+        out["loss_itm"] = sum(loss_itm) / len(loss_itm)
+    return out
 
 
 def _cap_inputs(self, batch):
@@ -203,17 +237,27 @@ def _cap_inputs(self, batch):
     return masked_ids, labels, m3
 
 
+def _twin_kv_own(self, offered, key):
+    """kv_own of the retrieval twin whose K/V memory a captioning sub-task of condition set `key` reads, None if it projects its own tokens.
+    offered: {condition set: (kv_own, kv_neg)} - in the direct step every memory once its triplet pass has projected it (enc["_cross_kv"]: a
+    captioning family in front of its retrieval twin finds nothing), in the staged step the memory of a condition set's only triplet."""
+    kv = offered.get(key) if _share_cross_kv(self) else None
+    return None if kv is None else kv[0]
+
+
+def _cap_loss(self, cap_in, *, kv_own=None, cond=None):
+    """The captioning pass and its loss (vast.py:500-512) over cap_in = _cap_inputs(...), against _twin_kv_own's memory or, without one, cond."""
+    masked_ids, labels, m3 = cap_in
+    return self.multimodal_encoder(input_ids=masked_ids, attention_mask=m3, labels=labels, cross_kv=None if kv_own is None else (kv_own, None),
+                                   encoder_hidden_states=cond if kv_own is None else None).loss
+
+
 def _forward_cap(self, batch, enc, subtasks):
-    masked_ids, labels, m3 = _cap_inputs(self, batch)
+    cap_in = _cap_inputs(self, batch)
     losses = []
     for st in subtasks:
-        kv = enc.get("_cross_kv", {}).get(st[1:]) if _share_cross_kv(self) else None
-        if kv is not None:   # the retrieval branch of this step already projected these condition tokens
-            losses.append(self.multimodal_encoder(input_ids=masked_ids, attention_mask=m3, cross_kv=(kv[0], None), labels=labels).loss)
-            continue
-        cond = _condition_feats(self, enc, st[1:])
-        losses.append(self.multimodal_encoder(input_ids=masked_ids, attention_mask=m3, encoder_hidden_states=cond,
-                                              labels=labels).loss)
+        kv_own = _twin_kv_own(self, enc.get("_cross_kv", {}), st[1:])
+        losses.append(_cap_loss(self, cap_in, kv_own=kv_own, cond=_condition_feats(self, enc, st[1:]) if kv_own is None else None))
     return {"loss_cap": sum(losses) / len(losses)}
 
 
@@ -239,10 +283,7 @@ def _qa_questions(self, batch):
     if any(isinstance(q, (list, tuple)) for q in raw):
         nq = [len(q) for q in raw]
         raw = [q for qs in raw for q in qs]
-    dev = self.contra_temp.device
-    tok = self.multimodal_encoder.tokenizer(list(raw), padding="max_length", truncation=True, max_length=self.max_caption_len,
-                                            return_tensors="pt")
-    return tok.input_ids.to(dev), tok.attention_mask.to(dev), nq
+    return _tokenize(self, list(raw), self.max_caption_len) + (nq,)
 
 
 def _qa_inputs(self, batch, q_ids, q_mask):
@@ -251,9 +292,7 @@ def _qa_inputs(self, batch, q_ids, q_mask):
     if "answer_ids" in batch:
         a_ids, a_mask = batch["answer_ids"], batch["answer_mask"]
     else:
-        tok = self.multimodal_encoder.tokenizer(list(batch["raw_answers"]), padding="max_length", truncation=True,
-                                                max_length=self.max_answer_len, return_tensors="pt")
-        a_ids, a_mask = tok.input_ids.to(q_ids.device), tok.attention_mask.to(q_ids.device)
+        a_ids, a_mask = _tokenize(self, list(batch["raw_answers"]), self.max_answer_len)
     if a_ids.shape[0] != q_ids.shape[0]:
         raise ValueError(f"forward_qa: {q_ids.shape[0]} questions for {a_ids.shape[0]} answers (training takes one question per sample)")
     inj = batch.get("_injected", {})
@@ -264,19 +303,23 @@ def _qa_inputs(self, batch, q_ids, q_mask):
     return torch.cat((q_ids, masked_ids), dim=1), labels, qa_attention_mask(q_mask, a_mask)
 
 
+def _cls_prompt(self, rows, device, prefix=None):
+    """The decoding prompt [prefix | [CLS]] and its 3-D mask (vast.py:618-623); prefix: (ids [rows, L], key-padding mask [rows, L]) or None."""
+    me = self.multimodal_encoder
+    cls = torch.full((rows, 1), me.tokenizer.bos_token_id, dtype=torch.long, device=device)
+    if prefix is None:
+        return cls, cls.new_ones(rows, 1, 1)
+    ids, m = prefix
+    return torch.cat((ids, cls), dim=1), me.update_attention_mask(m.unsqueeze(1).expand(-1, ids.shape[1], -1).contiguous())
+
+
 def _generate_text(self, cond, max_new_tokens, prefix=None, **search):
     """Decoded continuations of the prompt [prefix | [CLS]] under the condition tokens `cond`: BertForMaskedLM.generate (eos [SEP]; `search`:
     its beam-search or sampling arguments; config decode_use_cache: the cached decode), then the tokenizer over the new ids.
     prefix: (ids [rows, L], mask [rows, L]) or None - one prompt row [CLS] per condition set."""
     me = self.multimodal_encoder
     tk = me.tokenizer
-    if prefix is None:
-        prompt = torch.full((cond.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=cond.device)
-        mask = prompt.new_ones(cond.shape[0], 1, 1)
-    else:
-        ids, m = prefix
-        prompt = torch.cat((ids, torch.full((ids.shape[0], 1), tk.bos_token_id, dtype=torch.long, device=ids.device)), dim=1)
-        mask = me.update_attention_mask(m.unsqueeze(1).expand(-1, ids.shape[1], -1).contiguous())       # vast.py:618-623
+    prompt, mask = _cls_prompt(self, cond.shape[0] if prefix is None else prefix[0].shape[0], cond.device, prefix)
     out = me.generate(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=max_new_tokens,
                       eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=bool(self.config.get("decode_use_cache", False)),
                       **search)
@@ -293,12 +336,8 @@ def forward_qa(self, batch, task, compute_loss=True):
     eos [SEP], length penalty 1) from the prompt [question | [CLS]].  A sample may carry any number of questions (raw_questions as a list of
     lists, or num_questions); config decode_use_cache: the cached decode, each sample's condition tokens projected once and shared by its
     questions' rows (BertForMaskedLM.generate(rows_per_condition=...)), otherwise one copy of them per question as the reference makes."""
+    (_, subtasks), = _parse_task(task, "forward_qa")
     batch = dict(batch) if not isinstance(batch, dict) else batch
-    kind, *subtasks = task.split("%")
-    if kind != "qa" or not subtasks:
-        raise ValueError(f"forward_qa: task {task!r} is not of the form qa%<sub-task>%...")
-    for st in subtasks:
-        assert st in SUBTASKS, st
     enc = encode_batch(self, batch)
     q_ids, q_mask, num_questions = _qa_questions(self, batch)
     me = self.multimodal_encoder
@@ -341,12 +380,7 @@ def forward_scst(self, batch, task, reward_fn, num_samples=1, sample_noise=None)
     sample_noise: fp32 [b * num_samples, max_caption_len] uniform numbers in [0, 1) for the draws (or {sub-task: such a tensor}); None: torch's
     generator.  Returns {"loss_scst", "reward_sample", "reward_greedy" (means, fp32 scalars), "sampled_captions_<st>", "greedy_captions_<st>"}.
     No staged (backward_scale) form."""
-    kind, *subtasks = str(task).split("%")
-    if kind != "cap" or not subtasks or "_" in str(task):
-        raise ValueError(f"forward_scst: task {task!r} is not of the form cap%<sub-task>%...")
-    for st in subtasks:
-        if st not in SUBTASKS:
-            raise ValueError(f"forward_scst: unknown sub-task {st!r} in {task!r}")
+    (_, subtasks), = _parse_task(task, "forward_scst")
     if not callable(reward_fn):
         raise TypeError("forward_scst: reward_fn(captions, sample_index, batch) -> sequence of float is required (the project ships no reward)")
     K = int(num_samples)
@@ -359,13 +393,13 @@ def forward_scst(self, batch, task, reward_fn, num_samples=1, sample_noise=None)
     use_cache = bool(self.config.get("decode_use_cache", False))
     # (the towers and the condition packing only: the caption text is the reward's business, no text pass is needed here)
     enc = encode_batch(self, {k: v for k, v in batch.items() if k not in ("raw_captions", "input_ids", "attention_mask", "caption_tokens")})
-    out, losses, r_s_all, r_g_all = {}, [], [], []
+    out, losses, r_s_all, r_g_all, owner = {}, [], [], [], None
     for st in subtasks:
         cond = _condition_feats(self, enc, st[1:])
-        b, dev = cond.shape[0], cond.device
+        b = cond.shape[0]
+        owner = owner or [i // K for i in range(b * K)]      # the sample of each sampled row: one list for all sub-tasks
         noise = sample_noise.get(st) if isinstance(sample_noise, dict) else sample_noise
-        prompt = torch.full((b, 1), tk.bos_token_id, dtype=torch.long, device=dev)
-        mask = prompt.new_ones(b, 1, 1)
+        prompt, mask = _cls_prompt(self, b, cond.device)
         roll = dict(max_new_tokens=T, eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=use_cache)
         g_ids, _ = me.scst_rollout(prompt, mask, cond.detach(), do_sample=False, **roll)
         s_ids, _ = me.scst_rollout(prompt, mask, cond.detach(), do_sample=True, sample_noise=noise, num_return_sequences=K, **roll)
@@ -373,7 +407,6 @@ def forward_scst(self, batch, task, reward_fn, num_samples=1, sample_noise=None)
                                     eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id)
         caps_g = tk.batch_decode(g_ids[:, 1:], skip_special_tokens=True)
         caps_s = tk.batch_decode(s_ids[:, 1:], skip_special_tokens=True)
-        owner = [i // K for i in range(b * K)]
         r_g = torch.as_tensor(list(reward_fn(caps_g, list(range(b)), batch)), dtype=torch.float32, device=logp.device)
         r_s = torch.as_tensor(list(reward_fn(caps_s, owner, batch)), dtype=torch.float32, device=logp.device)
         if r_g.shape != (b,) or r_s.shape != (b * K,):
@@ -410,7 +443,11 @@ class _StagedLoss(torch.autograd.Function):
         return (None, None, None) + tuple(g.mul_(f) for g in grads) + (None,) * ctx.n
 
 
-def _forward_staged(self, batch, task, enc, scale):
+def _acc(total, term):
+    return term if total is None else total + term
+
+
+def _forward_staged(self, batch, families, enc, scale):
     """forward(compute_loss=True) with the BERT passes differentiated ONE CONDITION SET AT A TIME inside the forward (round 6).
     The direct form builds every ITM / captioning graph, their cross-attention K/V memories and, in the backward, their gradients on top of the
     towers' complete activation stash (profiles/r05_mem_trace.txt: the step's peak is the second triplet's BertFn.backward).  Here the towers'
@@ -419,60 +456,44 @@ def _forward_staged(self, batch, task, enc, scale):
     GradScaler's loss scale, 1.0 without one) - BERT-side parameter gradients go to .grad right away, the token gradients accumulate on the
     leaves, and the set's graph, K/V memory and gradient buffers are gone before the next set is built.  The returned losses carry one
     _StagedLoss node that hands the accumulated token gradients to the towers when the caller differentiates the sum.  Same loss values and
-    gradients as the direct form (same kernels on the same numbers; only the order in which autograd sums the token gradients differs);
-    random draws (hard negatives, token masks) happen in the direct form's order, BERT's per-pass dropout seeds are drawn in pass order, which
-    differs.  Contract: the caller calls backward() ONCE on scale * (unit-weight sum of the returned losses), after zero_grad - parameter
-    gradients of the BERT side are already in .grad when forward returns."""
-    ret_sub, cap_sub, out = [], [], {}
-    deferred = {}
-    for t in task.split("_"):
-        subtasks = t.split("%")[1:]
-        for st in subtasks:
-            assert st in SUBTASKS, st
-        if t.startswith("ret"):
+    gradients as the direct form (its _itm_loss and _cap_loss on the same numbers; only the order in which autograd sums the token gradients
+    differs); random draws (hard negatives, token masks) happen in the direct form's order, BERT's per-pass dropout seeds are drawn in pass
+    order, which differs.  families: _parse_task's list, none twice.  Contract: the caller calls backward() ONCE on scale * (unit-weight sum
+    of the returned losses), after zero_grad - parameter gradients of the BERT side are already in .grad when forward returns."""
+    ret_sub, cap_sub, out, deferred = [], [], {}, {}
+    for kind, subtasks in families:
+        if kind == "ret":
             out.update(_forward_ret(self, batch, enc, subtasks, deferred=deferred))
             ret_sub += subtasks
-        elif t.startswith("itc"):
+        elif kind == "itc":
             out.update(_forward_ret(self, batch, enc, subtasks, itm=False))
-        elif t.startswith("cap"):
-            cap_sub += subtasks
         else:
-            raise NotImplementedError(_UNKNOWN_FAMILY.format(t))
+            cap_sub += subtasks
     cap_in = _cap_inputs(self, batch) if cap_sub else None
-    keys = []
-    for st in ret_sub + cap_sub:
-        if st[1:] not in keys:
-            keys.append(st[1:])
     leaves = {}
     sums = {"loss_itm": None, "loss_cap": None}
-    from ..distributed import staged_backward
-    for key in keys:
+    for key in dict.fromkeys(st[1:] for st in ret_sub + cap_sub):      # the condition sets, in order of first mention
         for m in key:
             if m not in leaves:
                 leaves[m] = enc["condition_feats_" + m].detach().requires_grad_(True)
         cond = torch.cat([leaves[m] for m in key], dim=1) if len(key) > 1 else leaves[key]
-        total, kv = None, None
+        total, offered = None, {}
         itm_sts = [st for st in ret_sub if st[1:] == key]
         for st in itm_sts:
             d = deferred[st]
-            kv = self.multimodal_encoder.bert.project_cross_kv(cond, d["fetch"](cond, d["neg_c"]))
-            l = _itm_loss(self, kv, d["ids1"], d["am1"]) / len(ret_sub)
-            sums["loss_itm"] = l.detach() if sums["loss_itm"] is None else sums["loss_itm"] + l.detach()
-            total = l if total is None else total + l
+            kv = self.multimodal_encoder.bert.project_cross_kv(cond, d.fetch(cond, d.neg_c))
+            if len(itm_sts) == 1:      # (two triplets of one condition set: neither memory is the captioning pass's)
+                offered[key] = kv
+            l = _itm_loss(self, d.ids1, d.am1, kv=kv) / len(ret_sub)
+            sums["loss_itm"], total = _acc(sums["loss_itm"], l.detach()), _acc(total, l)
+            del kv
         for st in cap_sub:
-            if st[1:] != key:
-                continue
-            masked_ids, labels, m3 = cap_in
-            if kv is not None and len(itm_sts) == 1:     # the retrieval branch of this set projected these condition tokens
-                l = self.multimodal_encoder(input_ids=masked_ids, attention_mask=m3, cross_kv=(kv[0], None), labels=labels).loss
-            else:
-                l = self.multimodal_encoder(input_ids=masked_ids, attention_mask=m3, encoder_hidden_states=cond, labels=labels).loss
-            l = l / len(cap_sub)
-            sums["loss_cap"] = l.detach() if sums["loss_cap"] is None else sums["loss_cap"] + l.detach()
-            total = l if total is None else total + l
-        del kv
+            if st[1:] == key:
+                l = _cap_loss(self, cap_in, kv_own=_twin_kv_own(self, offered, key), cond=cond) / len(cap_sub)
+                sums["loss_cap"], total = _acc(sums["loss_cap"], l.detach()), _acc(total, l)
+        del offered
         runtime.mem_trace("staged set " + key + ": graph built")
-        with staged_backward():
+        with D.staged_backward():
             torch.autograd.backward(total * scale)
         del total, l, cond
         runtime.mem_trace("staged set " + key)
@@ -488,14 +509,46 @@ def _forward_staged(self, batch, task, enc, scale):
     return out
 
 
+def _eval_ret(self, batch, enc, subtasks):
+    """evaluation dict of vast.py:466-483: the text feature and tokens, per sub-task the contrastive feature and the condition tokens"""
+    ids, am = _tokens(self, batch)
+    out = dict(feat_t=enc["feat_t"], input_ids=ids, attention_mask=am)
+    for st in subtasks:
+        out[f"feat_cond_{st}"] = _feat_cond(self, enc, st[1:])
+        out[f"condition_feats_{st}"] = _condition_feats(self, enc, st[1:])
+    return out
+
+
+def _eval_cap(self, batch, enc, subtasks):
+    """evaluation dict of vast.py:513-547: beam-search captions per sub-task, or with config captioner_mode generate_nums sampled captions per
+    sample (top-k 10, vast.py:519-536), rows sample-major; with config decode_use_cache they share the sample's cross-attention K/V."""
+    out = {}
+    for st in subtasks:
+        cond = _condition_feats(self, enc, st[1:])
+        if self.config.get("captioner_mode", False):
+            gn = int(self.config.generate_nums)
+            cached = bool(self.config.get("decode_use_cache", False))
+            if not cached:      # a copy of the condition tokens per caption
+                cond = cond.unsqueeze(1).expand(-1, gn, -1, -1).reshape(-1, *cond.shape[1:]).contiguous()
+            search = dict(do_sample=True, top_k=10, sample_noise=(batch.get("_injected") or {}).get("sample_noise"),
+                          num_return_sequences=gn if cached else 1)
+        else:
+            search = dict(num_beams=self.beam_size, length_penalty=0.6)
+        out[f"generated_captions_{st}"] = _generate_text(self, cond, self.max_caption_len, **search)
+    return out
+
+
 def forward(self, batch, task, compute_loss=True, backward_scale=None):
-    """Returns {"loss_itc", "loss_itm", "loss_cap"} for task strings like "ret%tva%tv_cap%tva" (vast.py:317-348).  The question-answering
-    family ("qa%...") is not routed here - it raises NotImplementedError; call forward_qa.
+    """Returns {"loss_itc", "loss_itm", "loss_cap"} for task strings like "ret%tva%tv_cap%tva" (vast.py:317-348); compute_loss=False: _eval_ret /
+    _eval_cap.  The question-answering family ("qa%...") is not routed here - it raises NotImplementedError; call forward_qa.
     backward_scale (float; None = the direct form): staged differentiation, see _forward_staged - the factor the caller multiplies the summed
     losses with before its single backward() (1.0, or GradScaler.get_scale())."""
+    families = _parse_task(task, "forward")
+    kinds = [kind for kind, _ in families]
+    if "itc" in kinds and not compute_loss:
+        raise ValueError("itc%... is a training objective")
     batch = dict(batch) if not isinstance(batch, dict) else batch
     runtime.mem_trace("step start")
-    kinds = [t.split("%")[0] for t in task.split("_")]
     # (a task string that names a branch twice keeps the direct form, whose later branch overwrites the earlier one's losses - vast.py:317-348)
     staged = backward_scale is not None and compute_loss and torch.is_grad_enabled() and _share_cross_kv(self) and len(set(kinds)) == len(kinds)
     runtime.step_staged = staged      # (functional.tower_plan: a staged step needs less memory next to the towers' saved activations)
@@ -505,47 +558,17 @@ def forward(self, batch, task, compute_loss=True, backward_scale=None):
         runtime.step_staged = False   # (the plan is made inside the tower's forward: a tower pass outside MiCo.forward is priced as a direct step)
     runtime.mem_trace("after encode_batch")
     if staged:
-        return _forward_staged(self, batch, task, enc, float(backward_scale))
+        return _forward_staged(self, batch, families, enc, float(backward_scale))
     out = {}
-    for t in task.split("_"):
-        subtasks = t.split("%")[1:]
-        for st in subtasks:
-            assert st in SUBTASKS, st
-        if t.startswith("ret"):
-            if compute_loss:
-                out.update(_forward_ret(self, batch, enc, subtasks))
-                runtime.mem_trace("after forward_ret")
-            else:   # evaluation dict of vast.py:466-483
-                ids, am = _tokens(self, batch)
-                out.update(feat_t=enc["feat_t"], input_ids=ids, attention_mask=am)
-                for st in subtasks:
-                    out[f"feat_cond_{st}"] = _feat_cond(self, enc, st[1:])
-                    out[f"condition_feats_{st}"] = _condition_feats(self, enc, st[1:])
-        elif t.startswith("itc"):      # contrastive objective only (no ITM passes): step-A of SURVEY.md section 8d
-            assert compute_loss, "itc%... is a training objective"
+    for kind, subtasks in families:
+        if kind == "itc":      # contrastive objective only (no ITM passes): step-A of SURVEY.md section 8d
             out.update(_forward_ret(self, batch, enc, subtasks, itm=False))
-        elif t.startswith("cap"):
-            if compute_loss:
-                out.update(_forward_cap(self, batch, enc, subtasks))
-                runtime.mem_trace("after forward_cap")
-            else:   # evaluation dict of vast.py:513-547: beam-search captions per sub-task (captioner_mode sampling is not provided)
-                # config decode_use_cache: incremental decoding (BertForMaskedLM.generate(use_cache=True)); the rows of a sample share its
-                # condition tokens' cross-attention K/V instead of a copy each
-                for st in subtasks:
-                    cond = _condition_feats(self, enc, st[1:])
-                    if self.config.get("captioner_mode", False):
-                        # vast.py:519-536: generate_nums sampled captions per sample (top-k 10 sampling), rows sample-major
-                        gn = int(self.config.generate_nums)
-                        nrs = 1
-                        if self.config.get("decode_use_cache", False):
-                            nrs = gn
-                        else:
-                            cond = cond.unsqueeze(1).expand(-1, gn, -1, -1).reshape(-1, *cond.shape[1:]).contiguous()
-                        search = dict(do_sample=True, top_k=10, sample_noise=(batch.get("_injected") or {}).get("sample_noise"),
-                                      num_return_sequences=nrs)
-                    else:
-                        search = dict(num_beams=self.beam_size, length_penalty=0.6)
-                    out[f"generated_captions_{st}"] = _generate_text(self, cond, self.max_caption_len, **search)
+        elif not compute_loss:
+            out.update((_eval_ret if kind == "ret" else _eval_cap)(self, batch, enc, subtasks))
+        elif kind == "ret":
+            out.update(_forward_ret(self, batch, enc, subtasks))
+            runtime.mem_trace("after forward_ret")
         else:
-            raise NotImplementedError(_UNKNOWN_FAMILY.format(t))
+            out.update(_forward_cap(self, batch, enc, subtasks))
+            runtime.mem_trace("after forward_cap")
     return out

@@ -392,6 +392,83 @@ def test_staged_backward_equals_direct(setup, cuda):
         assert worst[1] < 2e-3, (key, worst)
 
 
+def _step_pass_events(b, task, staged):
+    """What test_step_pass_order expects of one training step: the caption's text pass of encode_batch, then the ITM triplets (3 b rows, each after
+    the projection of its [own | hard negative] K/V memory) and the captioning passes (b rows, labels) - in task order in the direct form, per
+    condition set in the staged one.  Every pass asks for its dropout seed as it starts."""
+    text, seed = ("bert", b, "text", False), ("seed",)
+    itm = [("kv", True), ("bert", 3 * b, "cross_kv", False), seed]
+    cap_shared, cap_own = [("bert", b, "cross_kv", True), seed], [("bert", b, "cond", True), seed]
+    return [text, seed] + {
+        # direct: tva triplet, tv triplet, the captioning pass reads tva's memory; staged: set "va" (triplet + captioning), then set "v"
+        ("ret%tva%tv_cap%tva", False): itm + itm + cap_shared,
+        ("ret%tva%tv_cap%tva", True): itm + cap_shared + itm,
+        # direct: the captioning passes come first and project their own K/V; staged: set "va" (cap%tva reads the triplet's memory), then "v"
+        ("cap%tv%tva_ret%tva", False): cap_own + cap_own + itm,
+        ("cap%tv%tva_ret%tva", True): itm + cap_shared + cap_own,
+        # no triplet at all: the captioning pass projects its own K/V in both forms
+        ("itc%tv_cap%tv", False): cap_own,
+        ("itc%tv_cap%tv", True): cap_own,
+    }[(task, staged)]
+
+
+def test_step_pass_order(setup, cuda):
+    """The order of the BERT passes of a training step, which of them read a shared cross-attention K/V memory and which project their own
+    condition tokens, and the order in which they draw their dropout seeds - direct and staged form, as literal lists."""
+    vtype, tag, m, sd = setup
+    if tag != "b16_d2":
+        pytest.skip("tower independent")
+    fx = golden(f"loss_{tag}.pt")
+    r = fx["W1"]
+    b = fx["meta"]["b"]
+    batch0 = to_dev(synth_inputs(dict(b=b, vision=2, audio=1, S=12), seed=1234), cuda)
+    me = m.multimodal_encoder
+    bert = me.bert
+    events, labelled, seeds = [], [False], iter(range(1, 1 << 20))
+    bert_forward, project, lm_forward = bert.forward, bert.project_cross_kv, me.forward
+
+    def rec_lm(*a, **kw):
+        labelled[0] = kw.get("labels") is not None
+        try:
+            return lm_forward(*a, **kw)
+        finally:
+            labelled[0] = False
+
+    def rec_bert(input_ids=None, attention_mask=None, encoder_hidden_states=None, **kw):
+        mode = "cross_kv" if kw.get("cross_kv") is not None else "cond" if encoder_hidden_states is not None else "text"
+        events.append(("bert", input_ids.shape[0], mode, labelled[0]))
+        return bert_forward(input_ids, attention_mask, encoder_hidden_states, **kw)
+
+    def rec_kv(cond_own, cond_neg=None):
+        events.append(("kv", cond_neg is not None))
+        return project(cond_own, cond_neg)
+
+    def rec_seed():
+        events.append(("seed",))
+        return next(seeds)
+
+    was_training = m.training
+    me.forward, bert.forward, bert.project_cross_kv, bert.dropout_seed_source = rec_lm, rec_bert, rec_kv, rec_seed
+    m.train()
+    try:
+        for task in ("ret%tva%tv_cap%tva", "cap%tv%tva_ret%tva", "itc%tv_cap%tv"):
+            for scale in (None, 1.0):
+                batch = dict(batch0)
+                batch["_injected"] = {st: {k: r["inj"][st][k] for k in ("neg_cond_idx", "neg_text_idx")} for st in ("tva", "tv")}
+                batch["_injected"]["cap"] = r["inj"]["cap"]
+                del events[:]
+                with runtime.precision(torch.float16):
+                    m.zero_grad(set_to_none=True)
+                    m(batch, task, compute_loss=True, backward_scale=scale)
+                print(task, "staged" if scale else "direct", events)
+                assert events == _step_pass_events(b, task, scale is not None), (task, scale)
+    finally:
+        del me.forward, bert.forward, bert.project_cross_kv
+        bert.dropout_seed_source = None
+        m.train(was_training)
+        m.zero_grad(set_to_none=True)
+
+
 def test_dkv_session_both_reader_orders(setup, cuda):
     """functional.DkvSession at the BertModel level, in BOTH orders of arrival: a triplet pass [own | neg | own] and an own-only pass read one shared
     K/V memory (BertModel.project_cross_kv); whichever is created last is differentiated first and writes the own set's gradient buffer, the other adds to

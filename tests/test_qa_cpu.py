@@ -87,6 +87,8 @@ def test_forward_qa_refuses_other_task_families():
         MiCo.forward_qa(None, {}, "cap%tv")
     with pytest.raises(ValueError, match="qa%"):
         MiCo.forward_qa(None, {}, "qa")
+    with pytest.raises(ValueError, match="zz"):                 # an unknown sub-task, before the model (None) is touched
+        MiCo.forward_qa(None, {}, "qa%zz")
 
 
 def test_abi_declares_and_exports_the_ragged_decode():

@@ -195,6 +195,11 @@ def test_forward_scst_is_a_method_and_forward_still_refuses():
     from mico_amd.model.mico import MiCo
     assert MiCo.forward_scst is MF.forward_scst
     assert "qa%" in MF._UNKNOWN_FAMILY or "qa" in MF._UNKNOWN_FAMILY
+    # malformed task strings are refused before the model (None) or the batch is touched
+    with pytest.raises(ValueError, match="zz"):
+        MF.forward(None, {}, "ret%zz")
+    with pytest.raises(NotImplementedError, match="forward_qa"):
+        MF.forward(None, {}, "foo%tv")
 
 
 def test_generate_argument_errors():

@@ -532,6 +532,48 @@ int mico_fbank_windows(const float* fbank, int T, int mel, const int* win, int n
                        float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Device-side audio front end (ABI 121): waveform -> 16 kHz -> Kaldi log-mel filterbank, the two steps model/audioprocessor.py:34-43 takes
+ * from torchaudio.  Both are restated from the published algorithms (torchaudio 2.x compliance/kaldi.py fbank, functional.resample); every
+ * table (window, twiddles, mel filters, resampling taps) is computed by the caller in double precision and rounded to fp32 once.
+ *  mico_kaldi_fbank: wave (fp32, any number of clips packed back to back, n_samples in all) -> out [T, mel_out] fp32 log-mel rows:
+ *     kaldi.fbank(wave * scale, num_mel_bins = mel, sample_frequency = 16000, frame_length = 25, frame_shift = 10), other arguments at
+ *     their defaults (snip_edges, no dither, remove_dc_offset, pre-emphasis 0.97, Povey window, power spectrum, no energy row).
+ *     Frame i is the 400 samples from frame_start[i] (device int64 [T]; NULL: i * 160); a sample outside [0, n_samples) reads as 0, so
+ *     no table can make the kernel read out of bounds.  Per frame: x * scale, minus the frame mean, y[j] = x[j] - 0.97 x[max(j - 1, 0)],
+ *     times window[j] (fp32 [400]), zero-padded to 512, real FFT (one 256-point complex radix-4 FFT + the split step; twiddle: fp32
+ *     [512][2] = cos, -sin of 2 pi m / 512), power of bins 0..255 (bin 256 carries no filter weight), filter b = sum over its
+ *     filt_bins[b] = (first bin, count) of filt_w[filt_off[b] + t] * power[first + t] taken in bin order by one lane, log(max(e, FLT_EPSILON))
+ *     (an empty filter and a silent frame give exactly logf(FLT_EPSILON) = -15.942385).  mel_out != mel: the row is resized along the mel
+ *     axis as F.interpolate(mode="bilinear", align_corners=False) does (source s = max((j + 0.5) * mel / mel_out - 0.5, 0), i0 = floor(s),
+ *     i1 = min(i0 + 1, mel - 1)) before it is stored (audioprocessor.py:42-43).  1 <= mel <= 256.  One wave per frame, four frames per
+ *     workgroup; a frame's bits depend on its 400 samples alone, not on T or on how clips are packed.
+ *  mico_resample_sinc: polyphase FIR of torchaudio.transforms.Resample (sinc_interp_hann): out[f * P + p] = sum_j taps[p * ldt + j] *
+ *     x[f * orig + j - width], j < K, x zero outside [0, n); n_out = ceil(P * n / orig) outputs are written.  orig / P: the two rates
+ *     divided by their gcd; taps: fp32 [P, ldt], 16-byte aligned, ldt a multiple of 4 >= K with zeros past K.  The input span of a
+ *     workgroup's 256 outputs ((1 + 254 / P) * orig + ldt samples) is staged in LDS and must fit 64 KiB (rates with a tiny gcd do not).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct mico_fbank_params {
+    const float* wave;
+    int64_t n_samples;
+    const int64_t* frame_start;
+    int T;
+    float scale;
+    const float* window;
+    const float* twiddle;
+    int mel;
+    int mel_out;
+    const int* filt_bins;
+    const int* filt_off;
+    const float* filt_w;
+    float* out;
+} mico_fbank_params;
+int mico_kaldi_fbank(const mico_fbank_params* p, void* stream);
+/* mico_struct_layout()'s table for mico_fbank_params (sizeof, field offsets in declaration order, -1); returns its length. */
+int mico_fbank_params_layout(int* out, int n);
+int mico_resample_sinc(const float* wave, int64_t n, const float* taps, int K, int ldt, int orig, int P, int width, float* out,
+                       int64_t n_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Optimizer step: the decoupled-weight-decay Adam of data/utils/build_optimizer.py:105-197,
  * one launch for a whole parameter group (multi-tensor).  Per element, in this order (fp32):
  *     m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g g;   p -= step_size * m / (sqrt(v) + eps);

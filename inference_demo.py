@@ -9,6 +9,12 @@ contract: reads log/hps.json, picks ckpt/model_step_<max>.pt, renames video->vis
 casts to fp32, nearest-interpolates the frame embeddings to max_*_sample_num and bilinearly interpolates the ViT position
 table to the requested resolution.  The demo then encodes the image and the texts, prints the text-to-image similarity, the ITM
 scores and a beam-search caption (BertForMaskedLM.generate, :161-174).
+
+    python inference_demo.py --synthetic evaclip01_giant --image some.jpeg --audio clip.wav   # + the audio-text similarity [1, texts]
+
+--audio FILE.wav: the clip goes from the file to the tower's windows on the device (AudioProcessor: PCM decode, resample to 16 kHz, Kaldi
+log-mel filterbank, normalise / window) and its similarity to every text is printed after the image's lines, through the encoder, pooling
+and heads of the ret%ta sub-task.
 """
 import argparse
 import json
@@ -148,7 +154,19 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=
     return out
 
 
-def main():
+@torch.no_grad()
+def run_audio_demo(model, audio_input, texts, device="cuda", max_length=30):
+    """audio_input: the windows of one clip [sample_num, target_length, mel] (AudioProcessor) -> audio-to-text similarity [1, len(texts)]:
+    the tower on the spectrogram windows, CLS pooling and contra_head_a against the text feature, as ret%ta forms them."""
+    audio_output = model.forward_audio_encoder(audio_input.to(device).unsqueeze(0))
+    feat_a = F.normalize(model.contra_head_a(model.pool_audio_for_contra(audio_output)), dim=-1)
+    tok = model.multimodal_encoder.tokenizer(texts, padding="max_length", truncation=True, max_length=max_length, return_tensors="pt")
+    caption_output = model.forward_multimodal_encoder(tok.input_ids.to(device), tok.attention_mask.to(device)).sequence_output
+    feat_t = F.normalize(model.contra_head_t(model.pool_text_for_contra(caption_output)), dim=-1)
+    return dict(feat_a=feat_a, feat_t=feat_t, sim_a2t=torch.matmul(feat_a, feat_t.permute(1, 0)))
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--pretrain_dir", default="MiCo-g")
     ap.add_argument("--synthetic", default=None, help="vision_encoder_type: build a synthetic pretrain dir instead of reading one")
@@ -158,7 +176,8 @@ def main():
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--use_cache", action="store_true", help="decode the caption incrementally (K/V cache; same caption)")
     ap.add_argument("--rerank", action="store_true", help="ITM scores through the retrieval evaluation path (indexed K/V memory; same scores)")
-    args = ap.parse_args()
+    ap.add_argument("--audio", default=None, help="a PCM .wav clip: its audio-to-text similarity [1, texts] is printed after the image's lines")
+    args = ap.parse_args(argv)
     device = "cuda"
     from mico_amd import runtime
     from mico_amd.model.imageprocessor import ImageProcessor
@@ -179,6 +198,14 @@ def main():
     print(out["captions"])
     if args.question:
         print(out["answers"])
+    if args.audio:
+        from mico_amd.model.audioprocessor import AudioProcessor
+        aproc = AudioProcessor(melbins=224, target_length=224, sample_num=opts.max_audio_sample_num, resize_melbin_num=224, training=False,
+                               device=device)
+        audio_input = aproc(args.audio)
+        if audio_input is None or not audio_input.is_cuda:      # unreadable (printed by the processor) or missing
+            raise SystemExit(f"cannot read {args.audio}")
+        print(run_audio_demo(model, audio_input, args.texts, device)["sim_a2t"])
 
 
 if __name__ == "__main__":

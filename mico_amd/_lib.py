@@ -62,6 +62,13 @@ class LnBwdParams(C.Structure):
     ]
 
 
+class FbankParams(C.Structure):
+    _fields_ = [
+        ("wave", c_vp), ("n_samples", c_i64), ("frame_start", c_vp), ("T", c_int), ("scale", c_f), ("window", c_vp), ("twiddle", c_vp),
+        ("mel", c_int), ("mel_out", c_int), ("filt_bins", c_vp), ("filt_off", c_vp), ("filt_w", c_vp), ("out", c_vp),
+    ]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/mico_hip.h one to one
 PROTOTYPES = {
     "mico_version": [],
@@ -129,6 +136,9 @@ PROTOTYPES = {
     "mico_l2norm_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp],
     "mico_image_preprocess": [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_vp],
     "mico_fbank_windows": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_f, c_f, c_vp, c_vp],
+    "mico_kaldi_fbank": [C.POINTER(FbankParams), c_vp],
+    "mico_fbank_params_layout": [C.POINTER(c_int), c_int],
+    "mico_resample_sinc": [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp],
     "mico_adamw_step": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp],
     "mico_grads_finite": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp],
     "mico_grad_sumsq": [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp, c_vp],
@@ -153,22 +163,24 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 120   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 121   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):
-    """sizeof and every field offset of the ctypes parameter structs against the layout the library was compiled with."""
-    n = l.mico_struct_layout(None, 0)
-    buf = (c_int * n)()
-    l.mico_struct_layout(buf, n)
+    """sizeof and every field offset of the ctypes parameter structs against the layout the library was compiled with
+    (mico_struct_layout: the four GEMM / attention / LayerNorm structs; mico_fbank_params_layout: the audio front end's, in the same format)."""
     table, cur = [], []
-    for v in buf:
-        if v == -1:
-            table.append(cur)
-            cur = []
-        else:
-            cur.append(v)
-    classes = (GemmEpilogue, AttnParams, LnFwdParams, LnBwdParams)
+    for fn in (l.mico_struct_layout, l.mico_fbank_params_layout):
+        n = fn(None, 0)
+        buf = (c_int * n)()
+        fn(buf, n)
+        for v in buf:
+            if v == -1:
+                table.append(cur)
+                cur = []
+            else:
+                cur.append(v)
+    classes = (GemmEpilogue, AttnParams, LnFwdParams, LnBwdParams, FbankParams)
     if len(table) != len(classes):
         raise MicoHipError(f"mico_struct_layout reports {len(table)} structs, this binding mirrors {len(classes)}")
     for cls, (size, *offs) in zip(classes, table):

@@ -508,6 +508,65 @@ int mico_logprob_fwd_bwd(const void* logits, int logits_dtype, int64_t ld, int64
  * A row without any finite logit has no distribution: token 0, logp -inf. */
 int mico_vocab_sample(const float* logits, int64_t ld, int rows, int cols, const float* u, unsigned char* unfinished, int eos_id, int pad_id,
                       int64_t* token, float* logp, void* stream);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Device-side beam search (ABI 122; BertForMaskedLM.generate(device_search=True)): the candidate selection and the bookkeeping of
+ * transformers==4.31 beam_search / BeamSearchScorer / BeamHypotheses (early_stopping False, one returned sequence) without a host visit.
+ * A "set" is one prompt row's nb beams, rows = sets * nb, set-major.  1 <= nb <= 8.
+ *  mico_beam_topk: per set the 2 nb best of its nb * V candidates, descending; EQUAL SCORES BY ASCENDING beam * V + token.
+ *     score = processed((logits[row, token] - max) - log(sum exp(logits[row, :V] - max))) + beam_scores[row], fp32.  logits: fp32 [rows, V] (ld), every row with
+ *     a finite entry.  done: one byte per set, a set whose byte is non-zero is skipped (its outputs are left as they are).  Processors
+ *     (transformers' order: they act on the log-probabilities; all off with ids NULL) over the row's ids[row * ld_ids .. + cur_len), int64:
+ *       rep_penalty p != 1: a seen token's s becomes s * p where s < 0, else s / p;
+ *       ngram n > 0: token t is -inf where ids[i .. i + n - 2] equals the last n - 1 ids and ids[i + n - 1] == t (n = 1: every seen token);
+ *       ban_eos != 0: eos_id is -inf.
+ *     An id outside [0, V) is never used as an index.  Limits (MICO_EINVAL before any launch): V >= 2 nb, nb * V < 2^31, 0 <= cur_len <= 512
+ *     and V <= 65536 with ids.  ws: rows * 2 nb * 8 bytes of scratch (the rows' own candidate lists).  One 256-thread workgroup per row
+ *     (two reads of the row: log-sum-exp, then selection into per-thread lists in LDS, merged), then one wave per set.
+ *     out_score fp32 / out_beam int32 / out_token int32: [sets, 2 nb].
+ *  mico_beam_step: one step's bookkeeping for every set, one wave each (p->cand_*: mico_beam_topk's outputs; cur_len = the length of the
+ *     rows of ids_in, < max_length).  Walks the 2 nb candidates in rank order: an eos candidate of rank < nb joins the set's n-best list (the
+ *     row's ids_in[:cur_len], scored (double)score / len_pow[cur_len]; when the list is full only if it beats `worst`, evicting the lowest -
+ *     BeamHypotheses.add), one of rank >= nb is skipped, the first nb others become the next beams: beam_scores[r], parent[r] (int64, the
+ *     source ROW), ids_out[r, :cur_len] = ids_in[parent[r], :cur_len], ids_out[r, cur_len] = token.  Then done |= list full and
+ *     worst >= (double)cand_score[0] / len_pow[cur_len + 1]; a set that turns done decrements *not_done.  A done set emits pad_id, score 0 and
+ *     its own rows as parents, and keeps its state.  len_pow: fp64 [max_length + 1], len ** length_penalty computed by the caller.
+ *  mico_beam_finalize: sets not done add their nb open beams (ids_in[:cur_len], beam_scores); per set the best hypothesis (the first of the
+ *     highest score in insertion order) goes to best_ids[set, :len], eos_id at [len] if len < max_length, pad_id after it; best_len[set] = len.
+ *  State (caller-allocated, zero-filled except worst = 1e9): hyp_ids int64 [sets, nb, max_length], hyp_len int32 [sets, nb], hyp_score fp64
+ *  [sets, nb] (insertion order), hyp_count int32 [sets], worst fp64 [sets], done uint8 [sets], not_done int32 [1] = sets.
+ * ------------------------------------------------------------------------------------------------------------- */
+int mico_beam_topk(const float* logits, int64_t ld, int sets, int nb, int V, const float* beam_scores, const unsigned char* done,
+                   const int64_t* ids, int64_t ld_ids, int cur_len, float rep_penalty, int ngram, int ban_eos, int eos_id,
+                   void* ws, float* out_score, int* out_beam, int* out_token, void* stream);
+typedef struct mico_beam_params {
+    int sets;
+    int nb;
+    int cur_len;
+    int max_length;
+    int eos_id;               /* -1: none */
+    int pad_id;
+    const float* cand_score;
+    const int* cand_beam;
+    const int* cand_token;
+    const double* len_pow;
+    const int64_t* ids_in;    /* [rows, max_length] */
+    int64_t* ids_out;         /* [rows, max_length], the other half of the double buffer (step only) */
+    float* beam_scores;
+    int64_t* parent;
+    int64_t* hyp_ids;
+    int* hyp_len;
+    double* hyp_score;
+    int* hyp_count;
+    double* worst;
+    unsigned char* done;
+    int* not_done;
+    int64_t* best_ids;        /* [sets, max_length] (finalize only) */
+    int* best_len;
+} mico_beam_params;
+int mico_beam_step(const mico_beam_params* p, void* stream);
+int mico_beam_finalize(const mico_beam_params* p, void* stream);
+/* mico_struct_layout()'s table for mico_beam_params (sizeof, field offsets in declaration order, -1); returns its length. */
+int mico_beam_params_layout(int* out, int n);
 /* Small exact-fp32 GEMM for the tiny heads and similarity matrices (contra heads, itm head, ITC logits; vast.py:405-408,
  * mico.py:36-52): C = alpha * opA(A) opB(B) + beta * C, same ta/tb convention as mico_gemm, any sizes, fp32 everywhere. */
 int mico_sgemm_small(int ta, int tb, int M, int N, int K, const float* A, int64_t lda, const float* B, int64_t ldb,

@@ -105,12 +105,15 @@ def write_synthetic_pretrain_dir(path, vision_encoder_type="evaclip01_giant", st
 
 
 @torch.no_grad()
-def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False, rerank=False, questions=None):
+def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False, rerank=False, questions=None, device_search=False,
+             no_repeat_ngram_size=0, repetition_penalty=1.0):
     """The retrieval + matching part of the reference's __main__ (inference_demo.py:128-158).  use_cache: the caption's beam search
     decodes incrementally (BertForMaskedLM.generate(use_cache=True)).  rerank: the ITM scores come from the retrieval evaluation path
     (mico_amd.evaluation.rerank_retrieval: the image's condition tokens projected once, every text reading them by index) instead of one
     copy of the tokens per text - the same scores.  questions (list[str]; None: none asked): the image's answers to them
-    (MiCo.forward_qa, vast.py:557-650) as "answers" - with use_cache the image's condition tokens are projected once for all questions."""
+    (MiCo.forward_qa, vast.py:557-650) as "answers" - with use_cache the image's condition tokens are projected once for all questions.
+    device_search: the caption's and the answers' beam search runs on the device (generate(device_search=True)); no_repeat_ngram_size /
+    repetition_penalty: generate()'s logits processors for both (0 / 1.0: off)."""
     image_input = image_input.to(device).unsqueeze(1)          # image as a 1 frame video
     video_output = model.forward_vision_encoder(image_input)
     feat_v = F.normalize(model.contra_head_v(model.pool_vision_for_contra(video_output)), dim=-1)
@@ -135,21 +138,31 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=
     cap_input = model.get_multimodal_forward_input_vision(video_output)
     tk = model.multimodal_encoder.tokenizer
     init_ids = torch.full((cap_input.size(0), 1), tk.bos_token_id, dtype=torch.long, device=device)
+    search = {}      # (only what is switched on is passed: the plain call stays the plain call)
+    if device_search:
+        search["device_search"] = True
+    if int(no_repeat_ngram_size):
+        search["no_repeat_ngram_size"] = int(no_repeat_ngram_size)
+    if float(repetition_penalty) != 1.0:
+        search["repetition_penalty"] = float(repetition_penalty)
     outputs = model.multimodal_encoder.generate(input_ids=init_ids, attention_mask=init_ids.new_ones(cap_input.size(0), 1, 1),
                                                 encoder_hidden_states=cap_input, max_new_tokens=model.max_caption_len,
                                                 num_beams=model.beam_size, eos_token_id=tk.sep_token_id,
-                                                pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=use_cache)
+                                                pad_token_id=tk.pad_token_id, length_penalty=0.6, use_cache=use_cache, **search)
     captions = tk.batch_decode(outputs[:, 1:], skip_special_tokens=True)
     out = dict(feat_v=feat_v, feat_t=feat_t, sim_t2v=sim_t2v, itm_scores=slice_scores, input_ids=input_ids,
                caption_ids=outputs, captions=captions)
     if questions:
         # every question is asked of the one image: one sample with len(questions) questions
-        before = model.config.get("decode_use_cache", False)
-        model.config["decode_use_cache"] = bool(use_cache)
+        keys = {"decode_use_cache": bool(use_cache), **{f"decode_{k}": v for k, v in search.items()}}
+        before = {k: model.config[k] for k in keys if k in model.config}
+        model.config.update(keys)
         try:
             qa = model.forward_qa({"vision_pixels": image_input, "raw_questions": [list(questions)]}, "qa%tv", compute_loss=False)
         finally:
-            model.config["decode_use_cache"] = before
+            for k in keys:
+                model.config.pop(k, None)
+            model.config.update(before)
         out["answers"] = qa["generated_answers_tv"]
     return out
 
@@ -175,6 +188,9 @@ def main(argv=None):
     ap.add_argument("--question", action="append", default=None, help="a question about the image (repeatable); the answers are printed")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--use_cache", action="store_true", help="decode the caption incrementally (K/V cache; same caption)")
+    ap.add_argument("--device_search", action="store_true", help="run the beam search itself on the device (same caption)")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0, metavar="N", help="no n-gram of this size twice in a caption (0: off)")
+    ap.add_argument("--repetition_penalty", type=float, default=1.0, metavar="P", help="penalty on tokens already in the caption (1: off)")
     ap.add_argument("--rerank", action="store_true", help="ITM scores through the retrieval evaluation path (indexed K/V memory; same scores)")
     ap.add_argument("--audio", default=None, help="a PCM .wav clip: its audio-to-text similarity [1, texts] is printed after the image's lines")
     args = ap.parse_args(argv)
@@ -192,7 +208,8 @@ def main(argv=None):
     image_input = proc(args.image)
     if image_input is None:
         raise SystemExit(f"cannot read {args.image}")
-    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache, rerank=args.rerank, questions=args.question)
+    out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache, rerank=args.rerank, questions=args.question,
+                   device_search=args.device_search, no_repeat_ngram_size=args.no_repeat_ngram_size, repetition_penalty=args.repetition_penalty)
     print(out["sim_t2v"])
     print(out["itm_scores"])
     print(out["captions"])

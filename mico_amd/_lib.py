@@ -69,6 +69,15 @@ class FbankParams(C.Structure):
     ]
 
 
+class BeamParams(C.Structure):
+    _fields_ = [
+        ("sets", c_int), ("nb", c_int), ("cur_len", c_int), ("max_length", c_int), ("eos_id", c_int), ("pad_id", c_int),
+        ("cand_score", c_vp), ("cand_beam", c_vp), ("cand_token", c_vp), ("len_pow", c_vp), ("ids_in", c_vp), ("ids_out", c_vp),
+        ("beam_scores", c_vp), ("parent", c_vp), ("hyp_ids", c_vp), ("hyp_len", c_vp), ("hyp_score", c_vp), ("hyp_count", c_vp),
+        ("worst", c_vp), ("done", c_vp), ("not_done", c_vp), ("best_ids", c_vp), ("best_len", c_vp),
+    ]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/mico_hip.h one to one
 PROTOTYPES = {
     "mico_version": [],
@@ -122,6 +131,10 @@ PROTOTYPES = {
                         c_vp, c_f, c_int, c_vp],
     "mico_logprob_fwd_bwd": [c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_f, c_vp],
     "mico_vocab_sample": [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
+    "mico_beam_topk": [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mico_beam_step": [C.POINTER(BeamParams), c_vp],
+    "mico_beam_finalize": [C.POINTER(BeamParams), c_vp],
+    "mico_beam_params_layout": [C.POINTER(c_int), c_int],
     "mico_sgemm_small": [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp],
     "mico_gelu_f32": [c_vp, c_vp, c_i64, c_vp],
     "mico_gelu_bwd_f32": [c_vp, c_vp, c_vp, c_i64, c_vp],
@@ -163,14 +176,14 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 121   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 122   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):
     """sizeof and every field offset of the ctypes parameter structs against the layout the library was compiled with
-    (mico_struct_layout: the four GEMM / attention / LayerNorm structs; mico_fbank_params_layout: the audio front end's, in the same format)."""
+    (mico_struct_layout: the four GEMM / attention / LayerNorm structs; mico_fbank_params_layout / mico_beam_params_layout: the audio front end's and the beam search's, in the same format)."""
     table, cur = [], []
-    for fn in (l.mico_struct_layout, l.mico_fbank_params_layout):
+    for fn in (l.mico_struct_layout, l.mico_fbank_params_layout, l.mico_beam_params_layout):
         n = fn(None, 0)
         buf = (c_int * n)()
         fn(buf, n)
@@ -180,7 +193,7 @@ def _check_struct_layout(l):
                 cur = []
             else:
                 cur.append(v)
-    classes = (GemmEpilogue, AttnParams, LnFwdParams, LnBwdParams, FbankParams)
+    classes = (GemmEpilogue, AttnParams, LnFwdParams, LnBwdParams, FbankParams, BeamParams)
     if len(table) != len(classes):
         raise MicoHipError(f"mico_struct_layout reports {len(table)} structs, this binding mirrors {len(classes)}")
     for cls, (size, *offs) in zip(classes, table):

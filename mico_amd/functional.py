@@ -2410,14 +2410,15 @@ class BertDecodeCache:
     def next_token_logits(self, ids, parent=None):
         """= BertForMaskedLM.next_token_logits(ids, mask, cond) of the recomputing path: fp32 logits [rows, vocab] of the [MASK] appended
         to ids.  The first call runs the prompt; every later one expects ids grown by one token (after reorder by `parent`, int64 [rows]
-        host tensor or None, when rows were re-ordered) and runs positions t - 1, t only."""
+        or None, when rows were re-ordered) and runs positions t - 1, t only.  A host `parent` that is the identity skips the re-gather; one
+        that lives on the device is never read back: the cache is re-gathered unconditionally."""
         rows, cur = ids.shape
         dummy = torch.full((rows, 1), self.mask_token_id, dtype=torch.long, device=ids.device)
         if self.filled == 0:
             return self.run(torch.cat([ids, dummy], 1), 0)
         if cur != self.filled:
             raise ValueError(f"BertDecodeCache: ids of length {cur} after a pass over {self.filled} positions (one token per step)")
-        if parent is not None and not torch.equal(parent.cpu(), torch.arange(rows)):
+        if parent is not None and (parent.is_cuda or not torch.equal(parent, torch.arange(rows))):
             self.reorder(parent)
         return self.run(torch.cat([ids[:, -1:], dummy], 1), cur - 1)
 

@@ -357,9 +357,10 @@ class BertForMaskedLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, max_new_tokens=20, num_beams=1,
                  eos_token_id=None, pad_token_id=None, length_penalty=1.0, do_sample=False, top_k=50, sample_noise=None,
-                 use_cache=False, num_return_sequences=1, rows_per_condition=None, **unused):
+                 use_cache=False, num_return_sequences=1, rows_per_condition=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                 min_length=0, min_new_tokens=0, device_search=False, done_check_every=1, **unused):
         """Beam search with the semantics of transformers==4.31 GenerationMixin.generate / BeamSearchScorer as the reference
-        calls it (inference_demo.py:164-171: num_beams 3, length_penalty 0.6, early_stopping False, no logits processors):
+        calls it (inference_demo.py:164-171: num_beams 3, length_penalty 0.6, early_stopping False, no logits processors by default):
         2*num_beams candidates per step, finished hypotheses scored sum_logprob / len**length_penalty, the "cannot improve"
         stop heuristic, finalisation with the open beams, eos-terminated pad-filled output.  The search bookkeeping runs on
         the host over 2*num_beams candidates per sample; the model step and log-softmax / top-k run on the device.
@@ -371,9 +372,33 @@ class BertForMaskedLM(nn.Module):
         rows_per_condition (beam search only; None: one prompt row per condition set): a sequence of ints, one per set of
         encoder_hidden_states - set s is read by rows_per_condition[s] consecutive prompt rows (question answering: a sample's questions;
         zero allowed).  With the cache each set is projected once and read through the ragged decode attention; without it the condition
-        tokens are expanded here, one copy per prompt row."""
+        tokens are expanded here, one copy per prompt row.
+        Logits processors (beam search only, all off by default; apply_logits_processors): repetition_penalty, no_repeat_ngram_size,
+        min_length (eos banned while a row is shorter, prompt included) / min_new_tokens (while fewer tokens have been generated).  They act
+        on the log-probabilities over a row's whole ids, prompt included, as in transformers' beam_search.  num_beams = 1 runs the same beam
+        program, so repetition_penalty follows beam_search's order there too (penalty on log-probabilities), not transformers' greedy_search
+        (penalty on raw logits); the two -inf processors are the same either way.
+        device_search (beam search only, num_beams <= 8): the search itself on the device - per step mico_beam_topk (log-softmax, processors,
+        the 2 num_beams best per prompt row; equal scores by ascending beam * vocab + token, where torch.topk leaves the order open) and
+        mico_beam_step (BeamSearchScorer's bookkeeping), mico_beam_finalize at the end; the host reads one counter of unfinished prompt rows
+        every done_check_every steps and the lengths once.  Steps taken after every row has finished change nothing, so the ids do not
+        depend on done_check_every.  Same ids as the host search wherever its decisions do not hang on an fp32 rounding of the log-softmax."""
         if unused:
             raise TypeError(f"generate(): unsupported arguments {sorted(unused)}")
+        pen, ngram, min_len, min_new = float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(min_new_tokens)
+        if pen <= 0:
+            raise ValueError(f"generate(): repetition_penalty = {repetition_penalty} (a positive number; 1: off)")
+        if ngram < 0 or min_len < 0 or min_new < 0:
+            raise ValueError(f"generate(): no_repeat_ngram_size {no_repeat_ngram_size}, min_length {min_length}, min_new_tokens {min_new_tokens}: "
+                             "none may be negative")
+        if int(done_check_every) < 1:
+            raise ValueError(f"generate(): done_check_every = {done_check_every} (at least 1)")
+        if device_search and int(num_beams) > ops.BEAM_NB_MAX:
+            raise ValueError(f"generate(): device_search takes num_beams <= {ops.BEAM_NB_MAX} (got {num_beams})")
+        processors = pen != 1.0 or ngram > 0 or min_len > 0 or min_new > 0
+        if do_sample and (processors or device_search or int(done_check_every) != 1):
+            raise ValueError("generate(): repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, device_search and "
+                             "done_check_every are provided for beam search only (do_sample=False)")
         rpc = None
         if rows_per_condition is not None:      # (checked before anything is launched)
             rpc = [int(r) for r in rows_per_condition]
@@ -410,6 +435,10 @@ class BertForMaskedLM(nn.Module):
         ids = input_ids.repeat_interleave(nb, dim=0)
         dec = self._model_step(ids, attention_mask.repeat_interleave(nb, dim=0), encoder_hidden_states,
                                nb if rpc is None else [r * nb for r in rpc], max_length, use_cache)
+        ban_eos = lambda n: eos_token_id is not None and (n < min_len or n - cur < min_new)      # n: the rows' length before the step
+        if device_search:
+            return self._device_beam_search(dec, ids, nb, max_length, eos_token_id, pad_token_id, length_penalty,
+                                            (pen, ngram, ban_eos) if processors else None, int(done_check_every))
         beam_scores = torch.zeros(B, nb, dtype=torch.float32, device=dev)
         beam_scores[:, 1:] = -1e9
         beam_scores = beam_scores.view(-1)
@@ -418,7 +447,11 @@ class BertForMaskedLM(nn.Module):
         parent = None
         while True:
             logits = dec.next_token_logits(ids, parent).float()
-            scores = torch.log_softmax(logits, dim=-1) + beam_scores[:, None]
+            if processors:
+                scores = apply_logits_processors(torch.log_softmax(logits, dim=-1), ids, eos_token_id, pen, ngram, ban_eos(ids.shape[1]))
+                scores = scores + beam_scores[:, None]
+            else:
+                scores = torch.log_softmax(logits, dim=-1) + beam_scores[:, None]
             V = scores.shape[-1]
             top_s, top_i = torch.topk(scores.view(B, nb * V), 2 * nb, dim=1, largest=True, sorted=True)
             top_s, top_i = top_s.cpu(), top_i.cpu()
@@ -466,6 +499,38 @@ class BertForMaskedLM(nn.Module):
                 out[b, lens[b]] = eos_token_id
         return out.to(dev)
 
+    def _device_beam_search(self, dec, ids0, nb, max_length, eos_token_id, pad_token_id, length_penalty, processors, check_every):
+        """generate()'s beam search with the search on the device: ids0 [sets nb, P] the prompt rows times nb; processors None or
+        (repetition_penalty, no_repeat_ngram_size, ban_eos(length) -> bool).  The rows' ids live in the two halves of an int64
+        [rows, max_length] double buffer (a step gathers the parents' prefixes from one half into the other); the model step sees the
+        filled columns as a view and re-gathers its cache by the device-side parents."""
+        dev = ids0.device
+        rows, cur = ids0.shape
+        sets = rows // nb
+        pad = int(pad_token_id) if pad_token_id is not None else 0
+        buf = [torch.full((rows, max_length), pad, dtype=torch.long, device=dev) for _ in range(2)]
+        buf[0][:, :cur] = ids0
+        beam_scores = torch.zeros(sets, nb, dtype=torch.float32, device=dev)
+        beam_scores[:, 1:] = -1e9
+        beam_scores = beam_scores.view(-1)
+        state = ops.BeamState(sets, nb, max_length, length_penalty, dev)
+        parent = torch.empty(rows, dtype=torch.long, device=dev)
+        cand, side, steps = None, 0, 0
+        while cur < max_length:
+            ids = buf[side][:, :cur]
+            logits = dec.next_token_logits(ids, parent if steps else None).float()
+            proc = {}
+            if processors is not None:
+                proc = dict(ids=ids, repetition_penalty=processors[0], no_repeat_ngram_size=processors[1], ban_eos=processors[2](cur),
+                            eos_token_id=eos_token_id)
+            cand = ops.beam_topk(logits, beam_scores, nb, done=state.done, out=cand, **proc)
+            ops.beam_step(state, cand, buf[side], buf[side ^ 1], cur, beam_scores, parent, eos_token_id=eos_token_id, pad_token_id=pad)
+            side, cur, steps = side ^ 1, cur + 1, steps + 1
+            if cur < max_length and steps % check_every == 0 and int(state.not_done.item()) == 0:      # the step's only host read
+                break
+        best, lens = ops.beam_finalize(state, buf[side], cur, beam_scores, eos_token_id=eos_token_id, pad_token_id=pad)
+        width = min(int(lens.max()) + 1, max_length) if sets else cur
+        return best[:, :width].contiguous()
 
     def _sample(self, dec, ids, max_length, top_k, eos_token_id, pad_token_id, noise):
         """Top-k sampling as the reference's captioner_mode asks transformers 4.31 for it (vast.py:526-536: do_sample=True, top_k=10,
@@ -593,6 +658,33 @@ class BertForMaskedLM(nn.Module):
         logprobs = self.sequence_logprobs(ids, attention_mask, cond, prompt_len=input_ids.shape[1], eos_token_id=eos_token_id,
                                           pad_token_id=pad_token_id)
         return (ids, logprobs, step_lp) if return_rollout_logprobs else (ids, logprobs)
+
+
+def apply_logits_processors(scores, ids, eos_token_id, repetition_penalty=1.0, no_repeat_ngram_size=0, ban_eos=False):
+    """transformers' RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and the eos ban of MinLength / MinNewTokensLength, in that
+    order, as one pure-torch function on any device: scores [rows, V] (beam search: log-probabilities) and the rows' whole ids [rows, cur]
+    -> processed scores (a new tensor).  A seen token's score s becomes s * p where s < 0, else s / p; with n = no_repeat_ngram_size > 0
+    token t is -inf where ids[i .. i + n - 2] equals the last n - 1 ids and ids[i + n - 1] == t (n = 1: every seen token; nothing while
+    cur < n); ban_eos: eos_token_id is -inf.  An id outside [0, V) names no score and is ignored (mico_beam_topk does the same)."""
+    rows, V = scores.shape
+    cur = ids.shape[1]
+
+    def marked(tok, keep):      # bool [rows, V]: the tokens tok[keep]; the rest go to a spare column
+        m = torch.zeros(rows, V + 1, dtype=torch.bool, device=scores.device)
+        return m.scatter_(1, torch.where(keep & (tok >= 0) & (tok < V), tok, torch.full_like(tok, V)), True)[:, :V]
+
+    if repetition_penalty != 1.0 and cur > 0:
+        penalised = torch.where(scores < 0, scores * repetition_penalty, scores / repetition_penalty)
+        scores = torch.where(marked(ids, torch.ones_like(ids, dtype=torch.bool)), penalised, scores)
+    n = int(no_repeat_ngram_size)
+    if n > 0 and cur >= n:
+        windows = ids.unfold(1, n, 1)                                   # [rows, cur - n + 1, n]
+        match = (windows[..., :-1] == ids[:, cur + 1 - n:].unsqueeze(1)).all(dim=-1)
+        scores = scores.masked_fill(marked(windows[..., -1], match), float("-inf"))
+    if ban_eos and eos_token_id is not None and 0 <= int(eos_token_id) < V:
+        scores = scores.clone()
+        scores[:, int(eos_token_id)] = float("-inf")
+    return scores
 
 
 class _RecomputingStep:

@@ -316,10 +316,18 @@ def _cls_prompt(self, rows, device, prefix=None):
 def _generate_text(self, cond, max_new_tokens, prefix=None, **search):
     """Decoded continuations of the prompt [prefix | [CLS]] under the condition tokens `cond`: BertForMaskedLM.generate (eos [SEP]; `search`:
     its beam-search or sampling arguments; config decode_use_cache: the cached decode), then the tokenizer over the new ids.
+    Beam search also reads the config keys decode_device_search (the search itself on the device), decode_repetition_penalty,
+    decode_no_repeat_ngram_size and decode_min_new_tokens (generate()'s logits processors); all default off.
     prefix: (ids [rows, L], mask [rows, L]) or None - one prompt row [CLS] per condition set."""
     me = self.multimodal_encoder
     tk = me.tokenizer
     prompt, mask = _cls_prompt(self, cond.shape[0] if prefix is None else prefix[0].shape[0], cond.device, prefix)
+    if not search.get("do_sample", False):
+        cfg = self.config
+        for key, arg, off in (("decode_device_search", "device_search", False), ("decode_repetition_penalty", "repetition_penalty", 1.0),
+                              ("decode_no_repeat_ngram_size", "no_repeat_ngram_size", 0), ("decode_min_new_tokens", "min_new_tokens", 0)):
+            if cfg.get(key, off) != off:
+                search.setdefault(arg, cfg.get(key))
     out = me.generate(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=max_new_tokens,
                       eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=bool(self.config.get("decode_use_cache", False)),
                       **search)

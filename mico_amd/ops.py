@@ -636,6 +636,118 @@ def vocab_sample(logits, u, *, cols=None, unfinished=None, eos_token_id=None, pa
     return token, logp
 
 
+BEAM_NB_MAX = 8   # largest num_beams of the device-side beam search (BEAM_NB_MAX in csrc/beam.hip)
+
+
+def beam_topk(logits, beam_scores, num_beams, *, cols=None, done=None, ids=None, cur_len=None, repetition_penalty=1.0,
+              no_repeat_ngram_size=0, ban_eos=False, eos_token_id=None, out=None):
+    """(score fp32, beam int32, token int32), each [sets, 2 num_beams]: per set of num_beams consecutive rows of the fp32 logits [rows, >= cols]
+    (any row stride) the 2 num_beams best of log_softmax(logits[row, :cols]) (processed) + beam_scores[row], descending, equal scores by
+    ascending beam * cols + token; see mico_beam_topk.  done: bool / uint8 [sets], a done set's outputs are left untouched (`out`: the three
+    tensors to write into).  ids int64 [rows, >= cur_len] (any row stride) switches the processors on: repetition_penalty,
+    no_repeat_ngram_size, ban_eos (eos_token_id at -inf)."""
+    nb = int(num_beams)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise MicoHipError(f"beam_topk takes a 2-D fp32 matrix with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    rows = logits.shape[0]
+    cols = int(cols) if cols is not None else logits.shape[1]
+    if not 0 < cols <= logits.shape[1]:
+        raise MicoHipError(f"beam_topk: cols = {cols} of a row of {logits.shape[1]}")
+    if nb < 1 or rows % nb:
+        raise MicoHipError(f"beam_topk: {rows} rows are not a whole number of sets of {nb} beams")
+    sets = rows // nb
+    if beam_scores.dtype != torch.float32 or beam_scores.numel() != rows or not beam_scores.is_contiguous():
+        raise MicoHipError("beam_topk: beam_scores is a contiguous fp32 [rows] tensor")
+    if done is not None and (done.dtype not in (torch.bool, torch.uint8) or done.numel() != sets or not done.is_contiguous()):
+        raise MicoHipError("beam_topk: done is a contiguous bool / uint8 [sets] tensor")
+    ld_ids = 0
+    if ids is not None:
+        cur_len = ids.shape[1] if cur_len is None else int(cur_len)
+        if ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[0] != rows or (ids.shape[1] and ids.stride(1) != 1) or cur_len > ids.shape[1]:
+            raise MicoHipError(f"beam_topk: ids is int64 [rows, >= cur_len] with unit column stride (got {ids.dtype} {tuple(ids.shape)})")
+        ld_ids = ids.stride(0) if rows > 1 else max(ids.stride(0), cur_len)
+    K = 2 * nb
+    dev = logits.device
+    if out is None:
+        out = (torch.empty(sets, K, dtype=torch.float32, device=dev), torch.empty(sets, K, dtype=torch.int32, device=dev),
+               torch.empty(sets, K, dtype=torch.int32, device=dev))
+    score, beam, token = out
+    for t, dt in ((score, torch.float32), (beam, torch.int32), (token, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (sets, K) or not t.is_contiguous():
+            raise MicoHipError("beam_topk: out is (fp32, int32, int32) contiguous [sets, 2 num_beams] tensors")
+    if rows == 0:
+        return score, beam, token
+    ws = torch.empty(rows * K, dtype=torch.int64, device=dev)
+    check(_lib.lib().mico_beam_topk(_p(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), cols), sets, nb, cols, _p(beam_scores),
+                                    _p(done), _p(ids), ld_ids, int(cur_len or 0), float(repetition_penalty), int(no_repeat_ngram_size),
+                                    int(bool(ban_eos)), -1 if eos_token_id is None else int(eos_token_id), _p(ws), _p(score), _p(beam), _p(token),
+                                    _st()), "mico_beam_topk")
+    return score, beam, token
+
+
+class BeamState:
+    """The device-side state of one beam search (mico_beam_step / mico_beam_finalize): per set of num_beams rows the n-best list of finished
+    hypotheses (ids, lengths, fp64 scores in insertion order, count, worst score), the sticky `done` byte, and the counter of sets not yet
+    done.  len_pow: len ** length_penalty for len = 0 .. max_length, computed here by Python and uploaded once, so the device divides by the
+    very numbers the host search divides by."""
+
+    def __init__(self, sets, num_beams, max_length, length_penalty, device):
+        self.sets, self.nb, self.max_length = int(sets), int(num_beams), int(max_length)
+        if not 1 <= self.nb <= BEAM_NB_MAX:
+            raise MicoHipError(f"BeamState: num_beams = {num_beams} (1 .. {BEAM_NB_MAX})")
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.len_pow = torch.tensor([float(n ** length_penalty) for n in range(self.max_length + 1)], dtype=torch.float64).to(device)
+        self.hyp_ids = z((self.sets, self.nb, self.max_length), torch.int64)
+        self.hyp_len, self.hyp_score = z((self.sets, self.nb), torch.int32), z((self.sets, self.nb), torch.float64)
+        self.hyp_count = z((self.sets,), torch.int32)
+        self.worst = torch.full((self.sets,), 1e9, dtype=torch.float64, device=device)
+        self.done = z((self.sets,), torch.uint8)
+        self.not_done = torch.full((1,), self.sets, dtype=torch.int32, device=device)
+
+    def params(self, cur_len, eos_token_id, pad_token_id, ids_in, beam_scores):
+        rows = self.sets * self.nb
+        if ids_in.dtype != torch.int64 or tuple(ids_in.shape) != (rows, self.max_length) or not ids_in.is_contiguous():
+            raise MicoHipError(f"beam search: ids buffers are contiguous int64 [{rows}, {self.max_length}] (got {ids_in.dtype} {tuple(ids_in.shape)})")
+        if beam_scores.dtype != torch.float32 or beam_scores.numel() != rows or not beam_scores.is_contiguous():
+            raise MicoHipError("beam search: beam_scores is a contiguous fp32 [rows] tensor")
+        p = _lib.BeamParams()
+        p.sets, p.nb, p.cur_len, p.max_length = self.sets, self.nb, int(cur_len), self.max_length
+        p.eos_id, p.pad_id = -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id or 0)
+        p.len_pow, p.ids_in, p.beam_scores = _p(self.len_pow), _p(ids_in), _p(beam_scores)
+        p.hyp_ids, p.hyp_len, p.hyp_score, p.hyp_count = _p(self.hyp_ids), _p(self.hyp_len), _p(self.hyp_score), _p(self.hyp_count)
+        p.worst, p.done, p.not_done = _p(self.worst), _p(self.done), _p(self.not_done)
+        return p
+
+
+def beam_step(state, cand, ids_in, ids_out, cur_len, beam_scores, parent, *, eos_token_id=None, pad_token_id=0):
+    """One step of the search bookkeeping on the device; see mico_beam_step.  cand: beam_topk's (score, beam, token); ids_in / ids_out: the two
+    halves of the int64 [rows, max_length] double buffer, rows of ids_in cur_len long; beam_scores fp32 [rows] and parent int64 [rows] are
+    written (the next step's scores; ids_out[r, :cur_len] = ids_in[parent[r], :cur_len], ids_out[r, cur_len] = the row's new token)."""
+    rows, K = state.sets * state.nb, 2 * state.nb
+    score, beam, token = cand
+    for t, dt in ((score, torch.float32), (beam, torch.int32), (token, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (state.sets, K) or not t.is_contiguous():
+            raise MicoHipError("beam_step: cand is beam_topk's (fp32, int32, int32) [sets, 2 num_beams] tensors")
+    if parent.dtype != torch.int64 or parent.numel() != rows or not parent.is_contiguous():
+        raise MicoHipError("beam_step: parent is a contiguous int64 [rows] tensor")
+    if tuple(ids_out.shape) != tuple(ids_in.shape) or ids_out.dtype != torch.int64 or not ids_out.is_contiguous() or ids_out.data_ptr() == ids_in.data_ptr():
+        raise MicoHipError("beam_step: ids_out is the other half of the ids double buffer")
+    p = state.params(cur_len, eos_token_id, pad_token_id, ids_in, beam_scores)
+    p.cand_score, p.cand_beam, p.cand_token, p.ids_out, p.parent = _p(score), _p(beam), _p(token), _p(ids_out), _p(parent)
+    check(_lib.lib().mico_beam_step(C.byref(p), _st()), "mico_beam_step")
+
+
+def beam_finalize(state, ids_in, cur_len, beam_scores, *, eos_token_id=None, pad_token_id=0):
+    """(best ids int64 [sets, max_length], lengths int32 [sets]): sets not done add their open beams (rows of ids_in, cur_len long, with
+    beam_scores), then every set's best hypothesis, eos-terminated and pad-filled; see mico_beam_finalize."""
+    p = state.params(cur_len, eos_token_id, pad_token_id, ids_in, beam_scores)
+    best = torch.empty(state.sets, state.max_length, dtype=torch.int64, device=ids_in.device)
+    lens = torch.empty(state.sets, dtype=torch.int32, device=ids_in.device)
+    p.best_ids, p.best_len = _p(best), _p(lens)
+    check(_lib.lib().mico_beam_finalize(C.byref(p), _st()), "mico_beam_finalize")
+    return best, lens
+
+
 def token_mask(tokens, mask_prob, u_mask, u_kind, u_tok, mask_token, range_start, range_end):
     """(masked token ids, labels) of the caption loss's TokenMasker on the device; see mico_token_mask.  u_mask [rounds, rows, S]."""
     rows, S = tokens.shape

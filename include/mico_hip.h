@@ -591,6 +591,34 @@ int mico_fbank_windows(const float* fbank, int T, int mel, const int* win, int n
                        float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Batched crop / resize / flip / normalise of decoded frames (ABI 123): the reference's `crop_flip` and `none` vision transforms
+ * (model/imageprocessor.py:25-40, model/videoprocessor.py:35-50; RandomResizedCrop + RandomHorizontalFlip in training, Resize +
+ * CenterCrop in evaluation, plain Resize for `none`) as ONE launch over n frames of any sizes.
+ *  mico_image_augment: src is one uint8 buffer of src_bytes bytes that holds the n RGB frames (H x W x 3, rows `pitch` bytes apart) back to
+ *  back at any byte offsets; dst is fp32 [n, 3, out_h, out_w]; table is a device int64 array [n, 12], one row per frame:
+ *     0 off    byte offset of the frame in src (any value, no alignment)      1 pitch   bytes per source row
+ *     2 top, 3 left, 4 ch, 5 cw    the source region that is sampled (the crop box, or the whole frame)
+ *     6 rh, 7 rw    size of the virtual resized image of that region           8 oy, 9 ox   where the out_h x out_w window sits in it
+ *     10 flip   0 / 1, horizontal flip of the output window                     11 reserved, 0
+ *  Output pixel (y, x) of a frame - torch's upsample_bilinear2d(align_corners = False) of the region, a window, a flip, Normalize:
+ *     xs = flip ? out_w - 1 - x : x;   Y = y + oy;   X = xs + ox;
+ *     sy = (float)ch / (float)rh,  sx = (float)cw / (float)rw   (divided in fp32)
+ *     fy = max(sy * (Y + 0.5f) - 0.5f, 0);   y0 = (int)fy;   y1 = min(y0 + 1, ch - 1);   ly = fy - y0;   hy = 1 - ly     (x likewise)
+ *     p00, p01, p10, p11 = region pixels (top + y0 | y1, left + x0 | x1), each times 1 / 255
+ *     v = hy * (hx * p00 + lx * p01) + ly * (hx * p10 + lx * p11)          (as mico_image_preprocess combines them)
+ *     dst[f, c, y, x] = (v - mean[c]) * istd[c]
+ *  Neighbours clamp at the REGION's edge (ch - 1, cw - 1), not the frame's: a pixel outside the crop box never reaches an edge sample, as
+ *  with torchvision, which crops first.  Every byte address is clamped into [0, src_bytes) before it is read, so no table entry can make
+ *  the kernel read outside src (a wrong table gives wrong pixels, never a fault); the host validates tables before a launch
+ *  (mico_amd/model/transforms.py).  A frame's bits depend on its table row and pixels alone, not on n or on its slot in the batch.
+ *  One thread produces four horizontally adjacent output pixels of all three planes (16-byte stores when out_w % 4 == 0 and dst is 16-byte
+ *  aligned, one 4-byte store per pixel otherwise: any out_w is legal).  MICO_EINVAL before any launch for a null pointer, n <= 0, src_bytes <= 0 or a
+ *  non-positive output size.
+ * ------------------------------------------------------------------------------------------------------------- */
+int mico_image_augment(const unsigned char* src, int64_t src_bytes, const int64_t* table, int n, float* dst, int out_h, int out_w,
+                       float mean0, float mean1, float mean2, float istd0, float istd1, float istd2, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Device-side audio front end (ABI 121): waveform -> 16 kHz -> Kaldi log-mel filterbank, the two steps model/audioprocessor.py:34-43 takes
  * from torchaudio.  Both are restated from the published algorithms (torchaudio 2.x compliance/kaldi.py fbank, functional.resample); every
  * table (window, twiddles, mel filters, resampling taps) is computed by the caller in double precision and rounded to fp32 once.

@@ -15,6 +15,13 @@ scores and a beam-search caption (BertForMaskedLM.generate, :161-174).
 --audio FILE.wav: the clip goes from the file to the tower's windows on the device (AudioProcessor: PCM decode, resample to 16 kHz, Kaldi
 log-mel filterbank, normalise / window) and its similarity to every text is printed after the image's lines, through the encoder, pooling
 and heads of the ret%ta sub-task.
+
+--transforms {none,crop_flip}: the reference's --vision_transforms, passed to the image processor and to the video processor of --video.  The
+demo runs in evaluation mode, so crop_flip is Resize(224) + CenterCrop(224) (the shorter side goes to 224, the central window is kept) instead
+of `none`'s Resize((224, 224)).
+
+--video FOLDER: a folder of extracted frames goes through VideoProcessor (max_vision_sample_num frames, decoded on the host, transformed on the
+device) and its similarity to every text is printed after the image's lines.
 """
 import argparse
 import json
@@ -168,6 +175,18 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=
 
 
 @torch.no_grad()
+def run_video_demo(model, video_input, texts, device="cuda", max_length=30):
+    """video_input: the frames of one clip [n, 3, r, r] (VideoProcessor) -> video-to-text similarity [1, len(texts)], formed as run_demo
+    forms the image's."""
+    video_output = model.forward_vision_encoder(video_input.to(device).unsqueeze(0))
+    feat_v = F.normalize(model.contra_head_v(model.pool_vision_for_contra(video_output)), dim=-1)
+    tok = model.multimodal_encoder.tokenizer(texts, padding="max_length", truncation=True, max_length=max_length, return_tensors="pt")
+    caption_output = model.forward_multimodal_encoder(tok.input_ids.to(device), tok.attention_mask.to(device)).sequence_output
+    feat_t = F.normalize(model.contra_head_t(model.pool_text_for_contra(caption_output)), dim=-1)
+    return dict(feat_v=feat_v, feat_t=feat_t, sim_v2t=torch.matmul(feat_v, feat_t.permute(1, 0)))
+
+
+@torch.no_grad()
 def run_audio_demo(model, audio_input, texts, device="cuda", max_length=30):
     """audio_input: the windows of one clip [sample_num, target_length, mel] (AudioProcessor) -> audio-to-text similarity [1, len(texts)]:
     the tower on the spectrogram windows, CLS pooling and contra_head_a against the text feature, as ret%ta forms them."""
@@ -193,6 +212,9 @@ def main(argv=None):
     ap.add_argument("--repetition_penalty", type=float, default=1.0, metavar="P", help="penalty on tokens already in the caption (1: off)")
     ap.add_argument("--rerank", action="store_true", help="ITM scores through the retrieval evaluation path (indexed K/V memory; same scores)")
     ap.add_argument("--audio", default=None, help="a PCM .wav clip: its audio-to-text similarity [1, texts] is printed after the image's lines")
+    ap.add_argument("--video", default=None, help="a folder of frames: its video-to-text similarity [1, texts] is printed after the image's lines")
+    ap.add_argument("--transforms", default="none", choices=["none", "crop_flip"],
+                    help="vision transforms of both processors (evaluation mode: crop_flip = resize the shorter side + centre crop)")
     args = ap.parse_args(argv)
     device = "cuda"
     from mico_amd import runtime
@@ -204,7 +226,8 @@ def main(argv=None):
         write_synthetic_pretrain_dir(args.pretrain_dir, args.synthetic)
     checkpoint, opts = load_from_pretrained_dir(args.pretrain_dir, video_resolution=224, return_modal="full")
     model = MiCo.from_pretrained(opts, checkpoint).to(device).eval()
-    proc = ImageProcessor(image_resolution=224, image_encoder_type="swin", training=True)
+    # (training only matters to crop_flip, which the demo wants in its evaluation form; `none` is the same transform either way)
+    proc = ImageProcessor(image_resolution=224, image_encoder_type="swin", image_transforms=args.transforms, training=args.transforms == "none")
     image_input = proc(args.image)
     if image_input is None:
         raise SystemExit(f"cannot read {args.image}")
@@ -215,6 +238,14 @@ def main(argv=None):
     print(out["captions"])
     if args.question:
         print(out["answers"])
+    if args.video:
+        from mico_amd.model.videoprocessor import VideoProcessor
+        vproc = VideoProcessor(video_resolution=224, video_encoder_type="swin", sample_num=opts.max_vision_sample_num,
+                               video_transforms=args.transforms, training=False, device=device)
+        video_input = vproc(args.video)
+        if video_input is None:      # unreadable (printed by the processor) or missing
+            raise SystemExit(f"cannot read {args.video}")
+        print(run_video_demo(model, video_input, args.texts, device)["sim_v2t"])
     if args.audio:
         from mico_amd.model.audioprocessor import AudioProcessor
         aproc = AudioProcessor(melbins=224, target_length=224, sample_num=opts.max_audio_sample_num, resize_melbin_num=224, training=False,

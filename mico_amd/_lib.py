@@ -149,6 +149,7 @@ PROTOTYPES = {
     "mico_l2norm_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp],
     "mico_image_preprocess": [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_vp],
     "mico_fbank_windows": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_f, c_f, c_vp, c_vp],
+    "mico_image_augment": [c_vp, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_vp],
     "mico_kaldi_fbank": [C.POINTER(FbankParams), c_vp],
     "mico_fbank_params_layout": [C.POINTER(c_int), c_int],
     "mico_resample_sinc": [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp],
@@ -176,7 +177,7 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 122   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 123   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):

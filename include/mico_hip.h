@@ -567,6 +567,64 @@ int mico_beam_step(const mico_beam_params* p, void* stream);
 int mico_beam_finalize(const mico_beam_params* p, void* stream);
 /* mico_struct_layout()'s table for mico_beam_params (sizeof, field offsets in declaration order, -1); returns its length. */
 int mico_beam_params_layout(int* out, int n);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Device-side sampling (ABI 124; BertForMaskedLM.sample(device_search=True)): one decode step of transformers==4.31 sample() for every row -
+ * logits processors on the raw logits, then the Temperature, TopK and TopP warpers, then ONE draw - without a host visit.
+ *  logits: fp32 [rows, V] (ld), finite or -inf.  u: fp32 [rows] uniform numbers in [0, 1) supplied by the caller.  token: int64 [rows].
+ *  1. Processors (all off with ids NULL) over the row's ids[row * ld_ids .. + cur_len), int64, on the raw logit x, by mico_beam_topk's rules:
+ *     rep_penalty p != 1: a seen token's x becomes x * p where x < 0, else x / p;  ngram n > 0: token t is -inf where ids[i .. i + n - 2] equals
+ *     the last n - 1 ids and ids[i + n - 1] == t;  ban_eos != 0: eos_id is -inf.  An id outside [0, V) is never used as an index.
+ *  2. s = x / temperature: one correctly rounded fp32 division (as are the penalty's product and quotient), so s is bit-equal to the same
+ *     statement in fp32 on the host and the selection by score needs no tolerance.
+ *  3. top_k > 0: exactly the min(top_k, V) best survive, by the total order of mico_topk_rows' keys: larger s first, EQUAL SCORES BY ASCENDING
+ *     COLUMN.  (transformers' TopKLogitsWarper keeps every column that ties with the k-th score; this keeps the first of them.)  0: off.
+ *  4. top_p: with the softmax over the survivors of 3., the candidate of descending rank r is kept iff the probability mass of the ranks ahead of
+ *     it is < top_p (TopPLogitsWarper with min_tokens_to_keep 1: rank 0 is always kept).  With top_k = 0 every column that holds the boundary
+ *     score is kept (a difference at exact ties on the boundary only), and the masses are sums of the fp32 weights e^(s - max), added in fp64 in
+ *     a fixed order (<= ceil(V / 256) terms per thread, then a 256-way tree), as is the draw's running sum.  top_p = 1: no cut, every finite
+ *     score is kept.
+ *  5. The draw, inverse-CDF by mico_vocab_sample's rule (the first candidate whose running sum of e^(s - max) exceeds u * total, `total` the running
+ *     sum's own last value; a candidate of zero weight is never drawn; a target rounded at or past the total gives the last candidate with a
+ *     weight).  The walk is in descending rank order with top_k > 0 (generate(do_sample=True, top_k >= 1)'s order) and in column order with
+ *     top_k = 0 (mico_vocab_sample's).
+ *  6. logp (may be NULL) = log-probability of the drawn token under the warped, renormalised distribution; n_kept int32 (may be NULL) = kept
+ *     candidates; kept_min fp32 (may be NULL) = the smallest kept s (top_k = 0: the kept set is s >= kept_min).  append != 0 with ids:
+ *     ids[row, cur_len] = token.
+ *  7. unfinished (may be NULL): one byte per row, in / out - a row whose byte is 0 emits pad_id, logp 0, n_kept 0 (and appends pad_id) and stays
+ *     0; a row that draws eos_id (-1: none) gets its byte cleared and decrements *not_done (int32, may be NULL).  A row without a finite score
+ *     has no distribution: token 0, logp -inf, n_kept 0, kept_min +inf.
+ *  Limits (MICO_EINVAL before any launch): 0 <= top_k <= 64, top_p in (0, 1], temperature > 0, V >= 1, ld >= V; with ids V <= 65536,
+ *  0 <= cur_len <= 512, ld_ids >= cur_len, and append needs cur_len < ld_ids.  One 256-thread workgroup per row, no allocation, no host
+ *  synchronisation, the same result for the same inputs.  Rows of V <= 34816 are staged in LDS as keys (one workgroup per CU).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct mico_warp_sample_params {
+    const float* logits;
+    int64_t ld;
+    int rows;
+    int V;
+    const float* u;
+    int64_t* ids;             /* [rows, ld_ids]; NULL: no processors, no append */
+    int64_t ld_ids;
+    int cur_len;
+    int top_k;                /* 0: off */
+    float top_p;
+    float temperature;
+    float rep_penalty;
+    int ngram;
+    int ban_eos;
+    int eos_id;               /* -1: none */
+    int pad_id;
+    unsigned char* unfinished;
+    int* not_done;
+    int append;
+    int64_t* token;
+    float* logp;
+    int* n_kept;
+    float* kept_min;
+} mico_warp_sample_params;
+int mico_warp_sample(const mico_warp_sample_params* p, void* stream);
+/* mico_struct_layout()'s table for mico_warp_sample_params (sizeof, field offsets in declaration order, -1); returns its length. */
+int mico_warp_sample_params_layout(int* out, int n);
 /* Small exact-fp32 GEMM for the tiny heads and similarity matrices (contra heads, itm head, ITC logits; vast.py:405-408,
  * mico.py:36-52): C = alpha * opA(A) opB(B) + beta * C, same ta/tb convention as mico_gemm, any sizes, fp32 everywhere. */
 int mico_sgemm_small(int ta, int tb, int M, int N, int K, const float* A, int64_t lda, const float* B, int64_t ldb,

@@ -113,14 +113,16 @@ def write_synthetic_pretrain_dir(path, vision_encoder_type="evaclip01_giant", st
 
 @torch.no_grad()
 def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=False, rerank=False, questions=None, device_search=False,
-             no_repeat_ngram_size=0, repetition_penalty=1.0):
+             no_repeat_ngram_size=0, repetition_penalty=1.0, sample_captions=0, top_k=10, top_p=1.0, temperature=1.0):
     """The retrieval + matching part of the reference's __main__ (inference_demo.py:128-158).  use_cache: the caption's beam search
     decodes incrementally (BertForMaskedLM.generate(use_cache=True)).  rerank: the ITM scores come from the retrieval evaluation path
     (mico_amd.evaluation.rerank_retrieval: the image's condition tokens projected once, every text reading them by index) instead of one
     copy of the tokens per text - the same scores.  questions (list[str]; None: none asked): the image's answers to them
     (MiCo.forward_qa, vast.py:557-650) as "answers" - with use_cache the image's condition tokens are projected once for all questions.
     device_search: the caption's and the answers' beam search runs on the device (generate(device_search=True)); no_repeat_ngram_size /
-    repetition_penalty: generate()'s logits processors for both (0 / 1.0: off)."""
+    repetition_penalty: generate()'s logits processors for both (0 / 1.0: off).
+    sample_captions N > 0: also N sampled captions of the image as "sampled_captions" (BertForMaskedLM.sample on the device: top_k, top_p,
+    temperature, and the two processors above)."""
     image_input = image_input.to(device).unsqueeze(1)          # image as a 1 frame video
     video_output = model.forward_vision_encoder(image_input)
     feat_v = F.normalize(model.contra_head_v(model.pool_vision_for_contra(video_output)), dim=-1)
@@ -159,6 +161,14 @@ def run_demo(model, image_input, texts, device="cuda", max_length=30, use_cache=
     captions = tk.batch_decode(outputs[:, 1:], skip_special_tokens=True)
     out = dict(feat_v=feat_v, feat_t=feat_t, sim_t2v=sim_t2v, itm_scores=slice_scores, input_ids=input_ids,
                caption_ids=outputs, captions=captions)
+    if int(sample_captions) > 0:
+        proc = {k: v for k, v in search.items() if k != "device_search"}
+        sampled = model.multimodal_encoder.sample(input_ids=init_ids, attention_mask=init_ids.new_ones(cap_input.size(0), 1, 1),
+                                                  encoder_hidden_states=cap_input, max_new_tokens=model.max_caption_len, top_k=int(top_k),
+                                                  top_p=float(top_p), temperature=float(temperature), eos_token_id=tk.sep_token_id,
+                                                  pad_token_id=tk.pad_token_id, num_return_sequences=int(sample_captions), use_cache=use_cache,
+                                                  **proc)
+        out["sampled_captions"] = tk.batch_decode(sampled[:, 1:], skip_special_tokens=True)
     if questions:
         # every question is asked of the one image: one sample with len(questions) questions
         keys = {"decode_use_cache": bool(use_cache), **{f"decode_{k}": v for k, v in search.items()}}
@@ -210,6 +220,10 @@ def main(argv=None):
     ap.add_argument("--device_search", action="store_true", help="run the beam search itself on the device (same caption)")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0, metavar="N", help="no n-gram of this size twice in a caption (0: off)")
     ap.add_argument("--repetition_penalty", type=float, default=1.0, metavar="P", help="penalty on tokens already in the caption (1: off)")
+    ap.add_argument("--sample_captions", type=int, default=0, metavar="N", help="also print N sampled captions (sampling decode on the device)")
+    ap.add_argument("--top_k", type=int, default=10, help="sampled captions: keep the K best tokens per step (0: off)")
+    ap.add_argument("--top_p", type=float, default=1.0, help="sampled captions: nucleus mass (1: off)")
+    ap.add_argument("--temperature", type=float, default=1.0, help="sampled captions: softmax temperature")
     ap.add_argument("--rerank", action="store_true", help="ITM scores through the retrieval evaluation path (indexed K/V memory; same scores)")
     ap.add_argument("--audio", default=None, help="a PCM .wav clip: its audio-to-text similarity [1, texts] is printed after the image's lines")
     ap.add_argument("--video", default=None, help="a folder of frames: its video-to-text similarity [1, texts] is printed after the image's lines")
@@ -232,10 +246,13 @@ def main(argv=None):
     if image_input is None:
         raise SystemExit(f"cannot read {args.image}")
     out = run_demo(model, image_input, args.texts, device, use_cache=args.use_cache, rerank=args.rerank, questions=args.question,
-                   device_search=args.device_search, no_repeat_ngram_size=args.no_repeat_ngram_size, repetition_penalty=args.repetition_penalty)
+                   device_search=args.device_search, no_repeat_ngram_size=args.no_repeat_ngram_size, repetition_penalty=args.repetition_penalty,
+                   sample_captions=args.sample_captions, top_k=args.top_k, top_p=args.top_p, temperature=args.temperature)
     print(out["sim_t2v"])
     print(out["itm_scores"])
     print(out["captions"])
+    if args.sample_captions > 0:
+        print(out["sampled_captions"])
     if args.question:
         print(out["answers"])
     if args.video:

@@ -78,6 +78,15 @@ class BeamParams(C.Structure):
     ]
 
 
+class WarpSampleParams(C.Structure):
+    _fields_ = [
+        ("logits", c_vp), ("ld", c_i64), ("rows", c_int), ("V", c_int), ("u", c_vp), ("ids", c_vp), ("ld_ids", c_i64), ("cur_len", c_int),
+        ("top_k", c_int), ("top_p", c_f), ("temperature", c_f), ("rep_penalty", c_f), ("ngram", c_int), ("ban_eos", c_int), ("eos_id", c_int),
+        ("pad_id", c_int), ("unfinished", c_vp), ("not_done", c_vp), ("append", c_int), ("token", c_vp), ("logp", c_vp), ("n_kept", c_vp),
+        ("kept_min", c_vp),
+    ]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/mico_hip.h one to one
 PROTOTYPES = {
     "mico_version": [],
@@ -135,6 +144,8 @@ PROTOTYPES = {
     "mico_beam_step": [C.POINTER(BeamParams), c_vp],
     "mico_beam_finalize": [C.POINTER(BeamParams), c_vp],
     "mico_beam_params_layout": [C.POINTER(c_int), c_int],
+    "mico_warp_sample": [C.POINTER(WarpSampleParams), c_vp],
+    "mico_warp_sample_params_layout": [C.POINTER(c_int), c_int],
     "mico_sgemm_small": [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp],
     "mico_gelu_f32": [c_vp, c_vp, c_i64, c_vp],
     "mico_gelu_bwd_f32": [c_vp, c_vp, c_vp, c_i64, c_vp],
@@ -177,14 +188,14 @@ class MicoHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 123   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
+ABI_VERSION = 124   # = mico_version() of the library this binding matches (bumped with every signature / struct change)
 
 
 def _check_struct_layout(l):
     """sizeof and every field offset of the ctypes parameter structs against the layout the library was compiled with
-    (mico_struct_layout: the four GEMM / attention / LayerNorm structs; mico_fbank_params_layout / mico_beam_params_layout: the audio front end's and the beam search's, in the same format)."""
+    (mico_struct_layout: the four GEMM / attention / LayerNorm structs; mico_fbank_params_layout / mico_beam_params_layout / mico_warp_sample_params_layout: the audio front end's, the beam search's and the sampling step's, in the same format)."""
     table, cur = [], []
-    for fn in (l.mico_struct_layout, l.mico_fbank_params_layout, l.mico_beam_params_layout):
+    for fn in (l.mico_struct_layout, l.mico_fbank_params_layout, l.mico_beam_params_layout, l.mico_warp_sample_params_layout):
         n = fn(None, 0)
         buf = (c_int * n)()
         fn(buf, n)
@@ -194,7 +205,7 @@ def _check_struct_layout(l):
                 cur = []
             else:
                 cur.append(v)
-    classes = (GemmEpilogue, AttnParams, LnFwdParams, LnBwdParams, FbankParams, BeamParams)
+    classes = (GemmEpilogue, AttnParams, LnFwdParams, LnBwdParams, FbankParams, BeamParams, WarpSampleParams)
     if len(table) != len(classes):
         raise MicoHipError(f"mico_struct_layout reports {len(table)} structs, this binding mirrors {len(classes)}")
     for cls, (size, *offs) in zip(classes, table):

@@ -592,6 +592,136 @@ class BertForMaskedLM(nn.Module):
         return ids, torch.stack(logps, dim=1)
 
     @torch.no_grad()
+    def sample(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, max_new_tokens=20, top_k=0, top_p=1.0, temperature=1.0,
+               repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=0, eos_token_id=None, pad_token_id=None,
+               num_return_sequences=1, use_cache=False, sample_noise=None, device_search=True, done_check_every=1, return_logprobs=False):
+        """Sampling decode with the semantics of transformers==4.31 sample(): per step the logits processors on the raw logits
+        (apply_logits_processors: repetition_penalty, no_repeat_ngram_size, the eos ban of min_length / min_new_tokens), then the warpers
+        (apply_logits_warpers: temperature, top_k - 0: off, at most ops.SAMPLE_TOPK_MAX -, top_p), then ONE draw per row by inverse CDF with
+        one uniform number per (row, step) - `sample_noise` [rows, max_new_tokens], or torch's generator.  The walk of the draw is in
+        descending score order with top_k >= 1 (the order of generate(do_sample=True, top_k >= 1), whose ids this returns when only top_k is
+        set) and in column order with top_k = 0 (the order of generate(do_sample=True, top_k=0)).  Rows that have produced eos emit pad from
+        then on.  num_return_sequences, use_cache and the row expansion as in generate()'s sampling branch.
+        device_search: the ids live in one int64 [rows, max_length] buffer; a step is one model step plus one mico_warp_sample, which also
+        appends the token and keeps the unfinished flags and their count on the device; the host reads that count every done_check_every
+        steps.  Steps taken after every row has finished only write pad, so the ids do not depend on done_check_every.
+        device_search=False: the same program in torch (the unfinished flags are read every step).
+        Returns ids [rows, <= max_length], trimmed after the step at which the last row finished; with return_logprobs also the per-step
+        log-probabilities of the drawn tokens under the warped distribution, fp32 [rows, steps], 0 on finished rows."""
+        k, top_p, temp, pen = int(top_k), float(top_p), float(temperature), float(repetition_penalty)
+        ngram, min_len, min_new, T = int(no_repeat_ngram_size), int(min_length), int(min_new_tokens), int(max_new_tokens)
+        nrs, check_every = int(num_return_sequences), int(done_check_every)
+        if not 0 <= k <= ops.SAMPLE_TOPK_MAX:
+            raise ValueError(f"sample(): top_k = {top_k} (0: no top-k warper; at most {ops.SAMPLE_TOPK_MAX})")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"sample(): top_p = {top_p} (in (0, 1]; 1: off)")
+        if not 0.0 < temp < float("inf"):
+            raise ValueError(f"sample(): temperature = {temperature} (a positive number)")
+        if pen <= 0:
+            raise ValueError(f"sample(): repetition_penalty = {repetition_penalty} (a positive number; 1: off)")
+        if ngram < 0 or min_len < 0 or min_new < 0:
+            raise ValueError(f"sample(): no_repeat_ngram_size {no_repeat_ngram_size}, min_length {min_length}, min_new_tokens {min_new_tokens}: "
+                             "none may be negative")
+        if T < 1 or nrs < 1:
+            raise ValueError(f"sample(): max_new_tokens = {max_new_tokens}, num_return_sequences = {num_return_sequences} (at least 1 each)")
+        if check_every < 1:
+            raise ValueError(f"sample(): done_check_every = {done_check_every} (at least 1)")
+        if sample_noise is not None and tuple(sample_noise.shape) != (input_ids.shape[0] * nrs, T):
+            raise ValueError(f"sample(): sample_noise is [rows, max_new_tokens] = [{input_ids.shape[0] * nrs}, {T}] uniform numbers")
+        if use_cache and self.training:
+            raise RuntimeError("sample(use_cache=True) is inference-only (the cached decode has no BERT dropout): call .eval() first")
+        if nrs > 1:
+            input_ids, attention_mask = input_ids.repeat_interleave(nrs, dim=0), attention_mask.repeat_interleave(nrs, dim=0)
+        P = input_ids.shape[1]
+        max_length = P + T
+        dec = self._model_step(input_ids, attention_mask, encoder_hidden_states, nrs, max_length, use_cache)
+        pad = int(pad_token_id) if pad_token_id is not None else 0
+        warp = dict(top_k=k, top_p=top_p, temperature=temp)
+        proc = dict(repetition_penalty=pen, no_repeat_ngram_size=ngram)
+        ban_eos = lambda n: eos_token_id is not None and (n < min_len or n - P < min_new)      # n: the rows' length before the step
+        run = self._device_sample if device_search else self._host_sample
+        ids, logps = run(dec, input_ids, max_length, warp, proc, ban_eos, eos_token_id, pad, sample_noise, check_every)
+        return (ids, logps) if return_logprobs else ids
+
+    def _device_sample(self, dec, ids0, max_length, warp, proc, ban_eos, eos_token_id, pad, noise, check_every):
+        """sample()'s loop with the step on the device (ops.warp_sample); returns (ids, logps)."""
+        dev = ids0.device
+        rows, P = ids0.shape
+        T = max_length - P
+        buf = torch.full((rows, max_length), pad, dtype=torch.long, device=dev)
+        buf[:, :P] = ids0
+        u = noise.to(dev, torch.float32).t().contiguous() if noise is not None else torch.rand(T, rows, device=dev)
+        logps = torch.zeros(T, rows, dtype=torch.float32, device=dev)
+        out = [torch.empty(rows, dtype=dt, device=dev) for dt in (torch.int64, torch.float32, torch.int32, torch.float32)]
+        unfinished = not_done = None
+        if eos_token_id is not None:
+            unfinished = torch.ones(rows, dtype=torch.uint8, device=dev)
+            not_done = torch.full((1,), rows, dtype=torch.int32, device=dev)
+        processors = proc["repetition_penalty"] != 1.0 or proc["no_repeat_ngram_size"] > 0 or any(ban_eos(n) for n in range(P, max_length))
+        steps = 0
+        while steps < T:
+            cur = P + steps
+            logits = dec.next_token_logits(buf[:, :cur]).float()
+            in_kernel = logits.shape[-1] <= 65536 and cur <= 512      # the processors' (and with them the append's) limits
+            if processors and not in_kernel:
+                raise ValueError(f"sample(): the device-side logits processors take a vocabulary <= 65536 and rows <= 512 ids "
+                                 f"(got {logits.shape[-1]}, {cur})")
+            ids_arg = dict(ids=buf, cur_len=cur, append=True, ban_eos=ban_eos(cur), **proc) if in_kernel else {}
+            out[1] = logps[steps]
+            ops.warp_sample(logits, u[steps], eos_token_id=eos_token_id, pad_token_id=pad, unfinished=unfinished, not_done=not_done,
+                            out=tuple(out), **warp, **ids_arg)
+            if not in_kernel:
+                buf[:, cur] = out[0]
+            steps += 1
+            if not_done is not None and steps < T and steps % check_every == 0 and int(not_done.item()) == 0:      # the step's only host read
+                break
+        width = T
+        if eos_token_id is not None:      # the step at which the last row finished (one read)
+            hit = buf[:, P:P + steps] == eos_token_id
+            first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, torch.full((rows,), steps, device=dev))
+            width = int(first.max()) if rows else steps
+        return buf[:, :P + width].contiguous(), logps[:width].t().contiguous()
+
+    def _host_sample(self, dec, ids, max_length, warp, proc, ban_eos, eos_token_id, pad, noise, check_every):
+        """sample()'s loop in torch: apply_logits_processors, apply_logits_warpers, the draw by a float64 CDF (in descending score order over
+        the top_k candidates as _sample walks it, in column order with top_k = 0); returns (ids, logps)."""
+        dev = ids.device
+        B = ids.shape[0]
+        k = warp["top_k"]
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        rows = torch.arange(B, device=dev)
+        step, logps = 0, []
+        while True:
+            scores = apply_logits_processors(dec.next_token_logits(ids).float(), ids, eos_token_id, ban_eos=ban_eos(ids.shape[1]), **proc)
+            warped, kept = apply_logits_warpers(scores, **warp)
+            u = noise[:, step].to(dev).double() if noise is not None else torch.rand(B, dtype=torch.float64, device=dev)
+            if k > 0:
+                top_s, top_i = torch.sort(warped, dim=-1, descending=True, stable=True)
+                top_s, top_i = top_s[:, :k], top_i[:, :k]
+                cdf = torch.softmax(top_s, dim=-1).double().cumsum(-1)
+                pick = (cdf < (u * cdf[:, -1])[:, None]).sum(-1).minimum(kept.sum(-1) - 1).clamp_min(0)
+                tok = top_i[rows, pick]
+            else:
+                w = torch.softmax(warped.double(), dim=-1)
+                cdf = w.cumsum(-1)
+                last = (torch.arange(w.shape[1], device=dev) * (w > 0)).amax(-1)      # the last column with a weight
+                tok = (cdf <= (u * cdf[:, -1])[:, None]).sum(-1).minimum(last)
+            lp = warped[rows, tok] - torch.logsumexp(warped, dim=-1)
+            empty = ~kept.any(-1)      # no finite score: token 0, log-prob -inf
+            tok = torch.where(empty, torch.zeros_like(tok), tok)
+            lp = torch.where(empty, torch.full_like(lp, float("-inf")), lp)
+            if eos_token_id is not None:
+                tok = torch.where(unfinished, tok, torch.full_like(tok, pad))
+                lp = torch.where(unfinished, lp, torch.zeros_like(lp))
+                unfinished = unfinished & (tok != eos_token_id)
+            ids = torch.cat([ids, tok.view(-1, 1)], dim=1)
+            logps.append(lp)
+            step += 1
+            if ids.shape[1] >= max_length or not bool(unfinished.any()):
+                break
+        return ids, torch.stack(logps, dim=1)
+
+    @torch.no_grad()
     def scst_rollout(self, input_ids, attention_mask, encoder_hidden_states, max_new_tokens, eos_token_id, pad_token_id, do_sample=True,
                      sample_noise=None, num_return_sequences=1, use_cache=True):
         """The no-grad roll-out of generate_scst: (ids [R n, P + T], the roll-out's own log P(chosen token) fp32 [R n, T]) for R prompt
@@ -685,6 +815,28 @@ def apply_logits_processors(scores, ids, eos_token_id, repetition_penalty=1.0, n
         scores = scores.clone()
         scores[:, int(eos_token_id)] = float("-inf")
     return scores
+
+
+def apply_logits_warpers(scores, top_k=0, top_p=1.0, temperature=1.0):
+    """transformers' TemperatureLogitsWarper, TopKLogitsWarper and TopPLogitsWarper (min_tokens_to_keep 1), in that order, as one pure-torch
+    function on any device: scores [rows, V] fp32 or fp64 (processed logits) -> (warped scores, -inf outside the kept set; kept mask, bool
+    [rows, V]).  s = scores / temperature; top_k > 0 keeps the min(top_k, V) best of a stable descending sort, so equal scores go by
+    ascending column (TopKLogitsWarper keeps every tie with the k-th score); top_p < 1 keeps, of the softmax over what is left, the candidate
+    of descending rank r iff the probability mass of the ranks ahead of it is < top_p, rank 0 always (ties in that same order; the masses
+    are summed in float64; top_p = 1: no cut).  A score of -inf is never kept.  mico_warp_sample does the same on the device."""
+    s = scores if temperature == 1.0 else scores / torch.tensor(float(temperature), dtype=scores.dtype, device=scores.device)
+    V = s.shape[-1]
+    ranked, order = torch.sort(s, dim=-1, descending=True, stable=True)
+    keep = ranked > float("-inf")
+    if int(top_k) > 0:
+        keep = keep & (torch.arange(V, device=s.device) < int(top_k))
+    if float(top_p) < 1.0:
+        probs = torch.softmax(ranked.double().masked_fill(~keep, float("-inf")), dim=-1)      # (float64 whatever the scores are)
+        before = torch.cat([torch.zeros_like(probs[:, :1]), probs.cumsum(-1)[:, :-1]], dim=-1)      # mass of the ranks ahead
+        head = torch.arange(V, device=s.device) == 0
+        keep = keep & ((before < float(top_p)) | head)
+    kept = torch.zeros_like(keep).scatter_(1, order, keep)
+    return s.masked_fill(~kept, float("-inf")), kept
 
 
 class _RecomputingStep:

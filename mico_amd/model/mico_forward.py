@@ -318,6 +318,8 @@ def _generate_text(self, cond, max_new_tokens, prefix=None, **search):
     its beam-search or sampling arguments; config decode_use_cache: the cached decode), then the tokenizer over the new ids.
     Beam search also reads the config keys decode_device_search (the search itself on the device), decode_repetition_penalty,
     decode_no_repeat_ngram_size and decode_min_new_tokens (generate()'s logits processors); all default off.
+    Sampling (do_sample in `search`) with the config key decode_device_sampling goes through BertForMaskedLM.sample instead (the step on the
+    device), which also reads decode_top_p, decode_temperature and the three processor keys above; with the key off nothing changes.
     prefix: (ids [rows, L], mask [rows, L]) or None - one prompt row [CLS] per condition set."""
     me = self.multimodal_encoder
     tk = me.tokenizer
@@ -328,9 +330,17 @@ def _generate_text(self, cond, max_new_tokens, prefix=None, **search):
                               ("decode_no_repeat_ngram_size", "no_repeat_ngram_size", 0), ("decode_min_new_tokens", "min_new_tokens", 0)):
             if cfg.get(key, off) != off:
                 search.setdefault(arg, cfg.get(key))
-    out = me.generate(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=max_new_tokens,
-                      eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=bool(self.config.get("decode_use_cache", False)),
-                      **search)
+    common = dict(input_ids=prompt, attention_mask=mask, encoder_hidden_states=cond, max_new_tokens=max_new_tokens,
+                  eos_token_id=tk.sep_token_id, pad_token_id=tk.pad_token_id, use_cache=bool(self.config.get("decode_use_cache", False)))
+    if search.get("do_sample", False) and self.config.get("decode_device_sampling", False):
+        cfg = self.config
+        warp = {arg: cfg.get(key) for key, arg in (("decode_top_p", "top_p"), ("decode_temperature", "temperature"),
+                                                   ("decode_repetition_penalty", "repetition_penalty"),
+                                                   ("decode_no_repeat_ngram_size", "no_repeat_ngram_size"),
+                                                   ("decode_min_new_tokens", "min_new_tokens")) if cfg.get(key, None) is not None}
+        out = me.sample(**common, **warp, **{k: v for k, v in search.items() if k != "do_sample"})
+    else:
+        out = me.generate(**common, **search)
     return tk.batch_decode(out[:, prompt.shape[1]:], skip_special_tokens=True)
 
 
@@ -529,7 +539,8 @@ def _eval_ret(self, batch, enc, subtasks):
 
 def _eval_cap(self, batch, enc, subtasks):
     """evaluation dict of vast.py:513-547: beam-search captions per sub-task, or with config captioner_mode generate_nums sampled captions per
-    sample (top-k 10, vast.py:519-536), rows sample-major; with config decode_use_cache they share the sample's cross-attention K/V."""
+    sample (top-k 10, vast.py:519-536), rows sample-major; with config decode_use_cache they share the sample's cross-attention K/V, with
+    decode_device_sampling the sampling step runs on the device (_generate_text)."""
     out = {}
     for st in subtasks:
         cond = _condition_feats(self, enc, st[1:])

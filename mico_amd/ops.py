@@ -748,6 +748,61 @@ def beam_finalize(state, ids_in, cur_len, beam_scores, *, eos_token_id=None, pad
     return best, lens
 
 
+SAMPLE_TOPK_MAX = 64   # largest top_k of mico_warp_sample (SAMPLE_K_MAX in csrc/sample.hip)
+
+
+def warp_sample(logits, u, *, cols=None, ids=None, cur_len=None, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0,
+                no_repeat_ngram_size=0, ban_eos=False, eos_token_id=None, pad_token_id=0, unfinished=None, not_done=None, append=False,
+                out=None):
+    """(token int64, logp fp32, n_kept int32, kept_min fp32), each [rows]: one sampling decode step per row of the fp32 logits [rows, >= cols]
+    (any row stride) with the uniform numbers u fp32 [rows] - logits processors, temperature, top-k (0: off, <= SAMPLE_TOPK_MAX), top-p, one
+    inverse-CDF draw; see mico_warp_sample.  ids int64 [rows, >= cur_len] (any row stride) switches the processors on (repetition_penalty,
+    no_repeat_ngram_size, ban_eos) and, with append, receives the token in column cur_len.  unfinished: bool / uint8 [rows], updated in place
+    (finished rows emit pad_token_id; a row that draws eos_token_id becomes finished and decrements not_done, int32 [1]).  out: the four
+    tensors to write into.  The kernel's limits are its own: a refused call raises MicoHipError before anything is launched."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise MicoHipError(f"warp_sample takes a 2-D fp32 matrix with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    rows = logits.shape[0]
+    cols = int(cols) if cols is not None else logits.shape[1]
+    if cols > logits.shape[1]:
+        raise MicoHipError(f"warp_sample: cols = {cols} of a row of {logits.shape[1]}")
+    if u.dtype != torch.float32 or u.numel() != rows:
+        raise MicoHipError("warp_sample: u is fp32 [rows]")
+    if unfinished is not None and (unfinished.dtype not in (torch.bool, torch.uint8) or unfinished.numel() != rows
+                                   or not unfinished.is_contiguous()):
+        raise MicoHipError("warp_sample: unfinished is a contiguous bool / uint8 [rows] tensor")
+    if not_done is not None and (not_done.dtype != torch.int32 or not_done.numel() != 1):
+        raise MicoHipError("warp_sample: not_done is an int32 [1] tensor")
+    ld_ids = 0
+    if ids is not None:
+        cur_len = ids.shape[1] if cur_len is None else int(cur_len)
+        if ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[0] != rows or (ids.shape[1] and ids.stride(1) != 1) or cur_len > ids.shape[1]:
+            raise MicoHipError(f"warp_sample: ids is int64 [rows, >= cur_len] with unit column stride (got {ids.dtype} {tuple(ids.shape)})")
+        ld_ids = ids.stride(0) if rows > 1 else ids.shape[1]
+        if append and ld_ids > ids.shape[1] <= cur_len:      # (a narrowed view: the kernel's own check sees the stride only)
+            raise MicoHipError(f"warp_sample: append writes column cur_len = {cur_len} of ids {tuple(ids.shape)}")
+    dev = logits.device
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int64, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
+               torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.float32, device=dev))
+    token, logp, n_kept, kept_min = out
+    for t, dt in ((token, torch.int64), (logp, torch.float32), (n_kept, torch.int32), (kept_min, torch.float32)):
+        if t.dtype != dt or t.numel() != rows or not t.is_contiguous():
+            raise MicoHipError("warp_sample: out is (int64, fp32, int32, fp32) contiguous [rows] tensors")
+    if rows == 0:
+        return token, logp, n_kept, kept_min
+    p = _lib.WarpSampleParams()
+    p.logits, p.ld, p.rows, p.V = _p(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), cols), rows, cols
+    p.u, p.ids, p.ld_ids, p.cur_len = _p(u.contiguous()), _p(ids), ld_ids, int(cur_len or 0)
+    p.top_k, p.top_p, p.temperature = int(top_k), float(top_p), float(temperature)
+    p.rep_penalty, p.ngram, p.ban_eos = float(repetition_penalty), int(no_repeat_ngram_size), int(bool(ban_eos))
+    p.eos_id, p.pad_id = -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id or 0)
+    p.unfinished, p.not_done, p.append = _p(unfinished), _p(not_done), int(bool(append))
+    p.token, p.logp, p.n_kept, p.kept_min = _p(token), _p(logp), _p(n_kept), _p(kept_min)
+    check(_lib.lib().mico_warp_sample(C.byref(p), _st()), "mico_warp_sample")
+    return token, logp, n_kept, kept_min
+
+
 def token_mask(tokens, mask_prob, u_mask, u_kind, u_tok, mask_token, range_start, range_end):
     """(masked token ids, labels) of the caption loss's TokenMasker on the device; see mico_token_mask.  u_mask [rounds, rows, S]."""
     rows, S = tokens.shape
